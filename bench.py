@@ -13,6 +13,10 @@ bucketed all-reduce).
 
     python bench.py --gpus N --steps K --warmup W          (N>1 under torch.distributed.run)
 
+A plain run sets up, warms up, times the K steps of the headline and prints its record.  ``--full``
+adds every comparison described below (the other precision, the native engine, the table and DP
+plans); ``--dump-outputs DIR`` writes what the last timed step computed (see ``_dump_outputs``).
+
 Precision: the headline ``value`` is the REFERENCE precision, fp32 end to end (the reference is
 fp32 everywhere: cublasSgemm / cuDNN FLOAT) -- fp32 activations, fp32 weights, fp32
 tables.  The big Linear GEMMs run the exact three-way split on the bf16 matrix cores (every fp32
@@ -21,27 +25,27 @@ accumulation: csrc/kernels/gemm_x3.hip), the small ones the f32-input MFMA
 (v_mfma_f32_16x16x4_f32); both are tested against float64 at the native fp32 kernel's accuracy
 and the record names the engine in ``config.fp32_gemm``.  The bf16 fast mode (bf16 activations /
 MFMA operands, fp32 master weights and accumulation) is measured afterwards in the same process
-and reported as a secondary field ``config.bf16`` (``--dtype bf16`` makes it the headline,
-``--no-secondary`` skips it).
+(``--full``) and reported as a secondary field ``config.bf16`` (``--dtype bf16`` makes it the
+headline, ``--no-secondary`` skips it).
 
 Plans (N > 1): the headline is the SOAP-SEARCHED plan (``--strategy search``, the default): rank 0
 runs the MCMC search over the MI355X execution simulator (budget ``--search-budget``, seeded with the
 hand plan; the reference's FFModel::optimize, src/runtime/model.cc:1093-1144) and every rank trains
-with that plan; ``config.search`` carries the simulated speedup, budget and wall seconds.  The hand
-plan the search was seeded with (table-wise / column-split embeddings + DP MLPs, dlrm_strategy) is
-then timed as ``config.table`` (``config.search_speedup_vs_table``).  Before training, the pick is
+with that plan; ``config.search`` carries the simulated speedup, budget and wall seconds.  With
+``--full`` the hand plan the search was seeded with (table-wise / column-split embeddings + DP MLPs,
+dlrm_strategy) is then timed as ``config.table`` (``config.search_speedup_vs_table``).  Before training, the pick is
 re-simulated against the table plan with every xGMI / all-reduce constant of the (spec-based)
 machine model at 0.5x and 2x; if it loses more than ``--robust-threshold`` (10 %) in any corner the
 headline runs the table plan instead (``config.search.sensitivity``, parallelism
 ``soap-searchN-robust-table``; profiles/search_sensitivity_mlperf.txt).
 
-SOAP vs DP (N > 1): after the headline plan, the same model / precision / batch is built and timed
+SOAP vs DP (N > 1, ``--full``): after the headline plan, the same model / precision / batch is built and timed
 under pure data parallelism -- every table replicated on every GPU and trained by touched-row
 exchange (each replica coalesces its lookups, one all-gather of (row, gradient) payloads, every
 replica applies them in rank order; no table-sized gradient) -- and reported as ``config.dp``
 with ``config.soap_speedup_vs_dp`` = value / dp.value (``--no-dp`` skips it).
 
-Native engine (N = 1, fp32): the same model, batch, steps and warm-up trained by the C++ plan compiler and
+Native engine (N = 1, fp32, ``--full``): the same model, batch, steps and warm-up trained by the C++ plan compiler and
 HIP engine alone (apps/c/dlrm_native_bench.c through libflexmi_native_c, a child process with no
 Python), reported as ``config.native_engine`` (``--no-native`` skips it).
 
@@ -92,6 +96,14 @@ def parse():
                     help="N>1: skip the pure data-parallel comparison run (config.dp / config.soap_speedup_vs_dp)")
     ap.add_argument("--no-table", action="store_true",
                     help="N>1 with --strategy search: skip the hand-plan comparison run (config.table)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every comparison: the other precision (config.bf16 / "
+                         "config.fp32), the native engine (N=1, config.native_engine), the hand plan and pure data "
+                         "parallelism (N>1, config.table / config.dp).  A plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step of the headline run computed "
+                         "(predictions, metric accumulators, updated weights; a seeded row sample of large tables) "
+                         "as DIR/<name>.npy in float32")
     ap.add_argument("--budget-s", type=float, default=1200.0,
                     help="wall budget of the whole command: a comparison run whose estimated time no longer fits "
                          "is skipped (config.<run>.skipped) instead of risking the already-measured headline")
@@ -139,20 +151,21 @@ def main():
     t_start = time.time()
     # the headline first: everything after it is a comparison whose failure must not lose it
     head = run_once(a, a.dtype, comm)
+    # the comparison runs: only with --full (a plain run stops at the headline)
     runs = []
-    if cuda and not a.no_secondary:
+    if a.full and cuda and not a.no_secondary:
         other = "bf16" if a.dtype == "fp32" else "fp32"
         runs.append((other, other, None))
-    if world > 1 and a.strategy == "search" and not a.no_table:
+    if a.full and world > 1 and a.strategy == "search" and not a.no_table:
         # the hand-written plan the search was seeded with (table-wise / column embeddings + DP MLPs)
         runs.append(("table", a.dtype, "table"))
-    if world > 1 and a.strategy != "dp" and not a.no_dp:
+    if a.full and world > 1 and a.strategy != "dp" and not a.no_dp:
         # the second half of the BASELINE metric: the same model, precision and batch under pure
         # data parallelism (replicated tables trained by touched-row all-gather, DP MLPs)
         runs.append(("dp", a.dtype, "dp"))
     extra = {name: guarded_run(a, comm, name, dt, strat, head, t_start) for name, dt, strat in runs}
     native = None
-    if cuda and world == 1 and not a.no_native and a.dtype == "fp32" and a.table_scale == 1.0:
+    if a.full and cuda and world == 1 and not a.no_native and a.dtype == "fp32" and a.table_scale == 1.0:
         native = native_run(a, t_start)
     if rank == 0:
         rec = head["rec"]
@@ -597,6 +610,8 @@ def _timed(a, comm, model, cfg, dcfg, dense_in, sparse, strategy, search, ex, t_
         rec["config"]["search"] = dict(search)
     if rank == 0 and a.profile:
         ex.timer.print_summary(file=sys.stderr)
+    if a.dump_outputs and name == "head":
+        _dump_outputs(a.dump_outputs, comm, ex)
     out = {"rec": rec, "el": el, "dtype": cfg.compute_dtype, "wall_s": time.time() - t_run}
     # release this configuration's device memory before the next one is built
     ex.release()
@@ -606,6 +621,63 @@ def _timed(a, comm, model, cfg, dcfg, dense_in, sparse, strategy, search, ex, t_
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
     return out
+
+
+DUMP_WHOLE = 1 << 20      # arrays up to this many elements (4 MB) are written whole
+DUMP_ROWS = 256           # of a larger one: this many touched rows and as many seeded random rows
+DUMP_TOTAL = 60 << 20     # bytes written per rank at the most
+
+
+def _dump_outputs(out_dir, comm, ex):
+    """``--dump-outputs DIR``: what the last timed step left with its caller, as float32 .npy files --
+    the predictions of its batch, the metric accumulators (loss and accuracy sums over every step so
+    far) and every weight after its update.  A weight of more than DUMP_WHOLE elements (the large
+    embedding tables) is sampled by rows: the rows its first DUMP_ROWS lookups of the last batch
+    touched, then DUMP_ROWS rows drawn with a fixed seed; ``<name>.rows.npy`` holds the row numbers.
+    Inputs and initial weights are seeded, so two runs with the same arguments write comparable
+    files (about 30 MB for the default configuration).  Each rank writes its own shards, without
+    collectives; ranks other than 0 add ``.rank<r>`` to the names."""
+    import re
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if comm.rank == 0 else f".rank{comm.rank}"
+
+    left = [DUMP_TOTAL]
+
+    def save(name, arr):
+        if arr.nbytes > left[0]:
+            print(f"[bench] --dump-outputs: {name} left out ({DUMP_TOTAL >> 20} MB in all)", file=sys.stderr)
+            return
+        left[0] -= arr.nbytes
+        np.save(os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", "_", name) + suffix + ".npy"), arr)
+
+    def host(t):
+        return t.detach().to("cpu", torch.float32).contiguous().numpy()
+
+    if ex.logits_buf is not None:
+        save("predictions", host(ex.logits_buf))
+    save("metrics", host(ex.metric_acc))
+    for k, e in enumerate(ex.wentries.values()):
+        if e.master is None:
+            continue
+        name = f"w{k:02d}_{e.param.name}"
+        w = e.master.reshape(e.shape)
+        if w.numel() <= DUMP_WHOLE:
+            save(name, host(w))
+            continue
+        w = w.reshape(w.shape[0], -1)
+        rows = []
+        idx = ex.local_buffer(e.op.inputs[0]) if e.sparse and e.op.inputs[0].guid in ex.home else None
+        if idx is not None:
+            # global row numbers of the last batch's first lookups -> rows of this shard
+            r = idx.reshape(-1)[:DUMP_ROWS].to("cpu", torch.int64) - e.box[0][0]
+            rows.append(r[(r >= 0) & (r < w.shape[0])])
+        n = max(1, min(DUMP_ROWS, w.shape[0], DUMP_WHOLE // w.shape[1]))
+        rows.append(torch.from_numpy(np.sort(np.random.default_rng(0).integers(0, w.shape[0], size=n))))
+        rows = torch.cat(rows)
+        save(name, host(w[rows.to(w.device)]))
+        save(name + ".rows", rows.numpy().astype(np.float64))
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ for arm in "$@"; do
   envs=""
   [ "$arm" != "-" ] && envs="$arm"
   echo "== arm $i: ${envs:-default}" >> $O/${TAG}_ab.txt
-  env $envs timeout -k 10 240 python3 $R/bench.py --steps 50 --warmup 10 > $O/${TAG}_arm$i.log 2>&1 || exit $?
+  env $envs timeout -k 10 240 python3 $R/bench.py --full --steps 50 --warmup 10 > $O/${TAG}_arm$i.log 2>&1 || exit $?
   grep '^{' $O/${TAG}_arm$i.log >> $O/${TAG}_ab.txt
 done
 exit 0

@@ -7,9 +7,9 @@ TAG=$1; shift
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
-timeout -k 10 300 python3 $R/bench.py --steps 20 --warmup 5 "$@" > $O/${TAG}_bench.log 2>&1 || exit $?
+timeout -k 10 300 python3 $R/bench.py --full --steps 20 --warmup 5 "$@" > $O/${TAG}_bench.log 2>&1 || exit $?
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace -d $O/${TAG}_prof -o run -- python3 $R/bench.py --steps 20 --warmup 5 "$@" > $O/${TAG}_prof.log 2>&1 || exit $?
+timeout -k 10 300 rocprofv3 --kernel-trace -d $O/${TAG}_prof -o run -- python3 $R/bench.py --full --steps 20 --warmup 5 "$@" > $O/${TAG}_prof.log 2>&1 || exit $?
 DB=$(find $O/${TAG}_prof -name "*results.db" | head -1)
 cd $R
 python3 tools/prof_summary.py $DB 27 > $O/${TAG}_kernels.txt 2>&1

@@ -61,9 +61,44 @@ def test_bench_single_process():
     _check(r, 1)
 
 
-def test_bench_two_ranks():
+def test_bench_plain_run_stops_at_the_headline():
+    """Without ``--full`` two ranks time the searched headline plan only: no table / DP comparison."""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
               "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+              "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch-per-gpu", "64",
+              "--search-budget", "200"])
+    _check(r, 2)
+    c = r["config"]
+    assert c["parallelism"] == "soap-search2" and c["search"]["budget"] == 200
+    assert not {"table", "dp", "bf16", "fp32", "native_engine", "soap_speedup_vs_dp"} & set(c)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """``--dump-outputs DIR``: float32 arrays of the last timed step (predictions, metrics, updated
+    weights), the same from run to run; the step count changes them."""
+    import numpy as np
+
+    def dump(d, steps):
+        _run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "1", "--config", "tiny",
+              "--batch-per-gpu", "64", "--dump-outputs", str(d)])
+        return {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    a, b, c = dump(tmp_path / "a", 2), dump(tmp_path / "b", 2), dump(tmp_path / "c", 3)
+    assert set(a) == set(b) == set(c) and {"predictions.npy", "metrics.npy"} < set(a)
+    assert any(f.startswith("w") for f in a)
+    assert a["predictions.npy"].shape[0] == 64
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.isfinite(a[f]).all(), f
+        # same inputs and seeds; the tolerance only allows for the summation order of threaded kernels
+        np.testing.assert_allclose(a[f], b[f], rtol=1e-5, atol=1e-7, err_msg=f)
+    assert not np.array_equal(a["metrics.npy"], c["metrics.npy"])
+    assert any(not np.allclose(a[f], c[f], rtol=1e-5, atol=1e-7) for f in a if f.startswith("w"))
+
+
+def test_bench_two_ranks():
+    r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2",
               "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch-per-gpu", "64"])
     _check(r, 2)
     _check_three_plans(r, 2)
@@ -76,7 +111,7 @@ def test_bench_self_launches_eight_ranks():
     env_keys = ("WORLD_SIZE", "RANK", "LOCAL_RANK")
     saved = {k: os.environ.pop(k) for k in env_keys if k in os.environ}
     try:
-        r = _run([sys.executable, "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1",
+        r = _run([sys.executable, "bench.py", "--full", "--gpus", "8", "--steps", "2", "--warmup", "1",
                   "--config", "mlperf", "--table-scale", "1e-4", "--batch-per-gpu", "64"])
     finally:
         os.environ.update(saved)
@@ -101,7 +136,7 @@ def test_bench_eight_ranks_mlperf_plan(strategy):
     pure DP or the SOAP search) compiled and stepped on 8 gloo ranks with scaled-down tables."""
     extra = ["--search-budget", "200"] if strategy == "search" else []
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
-              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "8",
+              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "8",
               "--steps", "2", "--warmup", "1", "--config", "mlperf", "--table-scale", "1e-4",
               "--batch-per-gpu", "64", "--strategy", strategy] + extra)
     _check(r, 8)
@@ -122,7 +157,7 @@ def test_bench_search_falls_back_to_the_robust_plan():
     forced: --robust-threshold -1 rejects any pick), the 8-rank MLPerf headline runs the table plan
     the search was seeded with, labelled as such, with the corner table's worst case recorded."""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
-              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "8",
+              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "8",
               "--steps", "2", "--warmup", "1", "--config", "mlperf", "--table-scale", "1e-4",
               "--batch-per-gpu", "64", "--search-budget", "200", "--robust-threshold", "-1", "--no-dp"])
     _check(r, 8)
@@ -139,7 +174,7 @@ def test_bench_comparison_failure_keeps_headline():
     build phase) becomes ``config.dp.error`` on every rank -- no hang in the next collective -- and
     the already-measured headline (and the table comparison) still come out as one JSON line."""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
-              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "8",
+              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "8",
               "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch-per-gpu", "64",
               "--search-budget", "200"], FM_BENCH_FAIL="dp@3")
     _check(r, 8)
@@ -153,7 +188,7 @@ def test_bench_wall_budget_skips_comparisons():
     """With no wall budget left after the headline, the comparison runs are skipped with a reason
     instead of being started (two gloo ranks)."""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2",
               "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch-per-gpu", "64", "--budget-s", "1"])
     _check(r, 2)
     for name in ("table", "dp"):
@@ -165,7 +200,7 @@ def test_bench_init_failure_keeps_headline():
     dp@1:init -- device allocation / weight init) is agreed on by both ranks: ``config.dp.error``,
     the headline kept, no hang."""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+              "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2",
               "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch-per-gpu", "64",
               "--search-budget", "200"], FM_BENCH_FAIL="dp@1:init")
     _check(r, 2)
@@ -180,7 +215,7 @@ def test_bench_step_failure_ends_the_job():
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", MASTER_ADDR="127.0.0.1", FM_BENCH_FAIL="dp@1:step")
     t0 = time.time()
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
+                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "2",
                         "--steps", "2", "--warmup", "1", "--config", "tiny", "--batch-per-gpu", "64",
                         "--search-budget", "200"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode != 0, p.stdout[-2000:]

@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "flexmi", "libflexmi_native_c.so")
-REF_PB = "/root/reference/src/runtime/dlrm_strategy_8embs_8gpus.pb"
+REF_PB = os.path.join(ROOT, "tests", "golden", "dlrm_strategy_8embs_8gpus.pb")
 
 
 @pytest.fixture(scope="module")
@@ -43,7 +43,7 @@ def test_native_c_program(demo):
     x = rng.rand(20, 13).astype(np.float32)
     h5 = str(d / "d.h5")
     write_h5(h5, {"X_int": x, "y": rng.rand(20).astype(np.float32)})
-    args = [exe, str(d), h5] + ([REF_PB] if os.path.exists(REF_PB) else [])
+    args = [exe, str(d), h5, REF_PB]
     p = subprocess.run(args, capture_output=True, text=True, timeout=120, env=dict(os.environ, PYTHONHOME="/nonexistent"))
     assert p.returncode == 0, p.stdout + p.stderr
     out = p.stdout

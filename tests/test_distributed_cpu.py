@@ -121,9 +121,7 @@ def _build(case, world):
                 assert sum(len(pc.device_ids) == world and pc.dims[0] == world for pc in strat.values()) >= 4
             else:
                 from flexmi.parallel.strategy import load_strategies_from_file
-                ref = "/root/reference/src/runtime/dlrm_strategy_8embs_8gpus.pb"
-                if not os.path.exists(ref):
-                    pytest.skip("reference strategy file not available")
+                ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dlrm_strategy_8embs_8gpus.pb")
                 strat = load_strategies_from_file(ref)
     elif case.startswith("dlrm"):
         dcfg = DLRMConfig.preset("tiny")

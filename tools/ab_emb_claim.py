@@ -12,5 +12,5 @@ claim = sys.argv[1] == "1"
 import flexmi.ops.embedding as E  # noqa: E402
 
 E.Embedding.CLAIM = claim
-sys.argv = ["bench.py", "--steps", "50", "--warmup", "10", "--no-native"] + sys.argv[2:]
+sys.argv = ["bench.py", "--full", "--steps", "50", "--warmup", "10", "--no-native"] + sys.argv[2:]
 runpy.run_path("bench.py", run_name="__main__")
