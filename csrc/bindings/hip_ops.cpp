@@ -66,6 +66,9 @@ void fm_sdp_coalesce(int n, const void* const* idx, const int* idx64, const void
 void fm_sdp_apply_segments(int n, int segs, int own_seg, float* const* W, const int* D, const int* const* seg_ids,
                            const float* const* seg_g, const int* const* seg_count, int* const* slot, int* const* own_count,
                            const int* nmax, const float* lr, hipStream_t st);
+void fm_emb_adagrad_apply(int n, float* const* W, float* const* H, const int* D, const int* const* ids,
+                          const float* const* g, int* const* count, int* const* slot, const int* nmax, const float* lr,
+                          float eps, hipStream_t st);
 void fm_strided_copy4_run(const void* src, void* dst, int bf16, const int* d, const long* ss, const long* ts, long so,
                           long to, int acc, hipStream_t st);
 void fm_dot_interaction_fwd(const void* const* z, int F, long ldz, void* out, long ldo, long B, int D, int W, int self,
@@ -78,6 +81,8 @@ void fm_dot_interaction_bwd_f32(const float* const* z, int F, long ldz, const fl
                                 long lddz, unsigned acc_mask, long B, int D, int self, int act0, hipStream_t s);
 void fm_sgd_update(float* W, float* G, float* V, unsigned short* Wc, const float* lr, long n, float wd, float mom,
                    int nesterov, int zero_g, hipStream_t s);
+void fm_adagrad_update(float* W, float* G, float* H, unsigned short* Wc, const float* lr, long n, float wd, float eps,
+                       int zero_g, hipStream_t s);
 void fm_adam_update(float* W, float* G, float* M, float* V, unsigned short* Wc, long n, const float* alpha_t,
                     float b1, float b2, float wd, float eps, int zero_g, hipStream_t s);
 void fm_cast_bf16(const float* src, unsigned short* dst, long n, hipStream_t s);
@@ -568,6 +573,53 @@ void sdp_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> seg_ids,
                         po.data(), nmax.data(), lr.data_ptr<float>(), cur());
 }
 
+// fused sparse Adagrad (embedding.hip): one coalesced payload (ids, g, count) per table ->
+// H[ids] += g g, W[ids] -= lr g / (sqrt(H[ids]) + eps); frees the slots and zeroes the counts
+void emb_adagrad_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> H, std::vector<torch::Tensor> ids,
+                       std::vector<torch::Tensor> g, std::vector<torch::Tensor> count, std::vector<torch::Tensor> slot,
+                       torch::Tensor lr, double eps) {
+  const size_t n = W.size();
+  if (n == 0) return;
+  TORCH_CHECK(H.size() == n && ids.size() == n && g.size() == n && count.size() == n && slot.size() == n,
+              "emb_adagrad_apply: one buffer of each kind per table");
+  check_cuda(lr, "lr");
+  TORCH_CHECK(lr.scalar_type() == torch::kFloat32 && lr.numel() >= 1, "lr: fp32 device scalar");
+  std::vector<float*> pw, ph;
+  std::vector<int> D, nmax;
+  std::vector<const int*> pi;
+  std::vector<const float*> pg;
+  std::vector<int*> pn, ps;
+  for (size_t k = 0; k < n; ++k) {
+    check_cuda(W[k], "W");
+    check_cuda(H[k], "H");
+    check_cuda(ids[k], "ids");
+    check_cuda(g[k], "g");
+    check_cuda(count[k], "count");
+    check_cuda(slot[k], "slot");
+    TORCH_CHECK(W[k].scalar_type() == torch::kFloat32 && W[k].is_contiguous() && W[k].dim() == 2, "tables fp32 [rows, D]");
+    TORCH_CHECK(H[k].scalar_type() == torch::kFloat32 && H[k].is_contiguous() && H[k].sizes() == W[k].sizes(),
+                "adagrad H: fp32, the table's shape");
+    TORCH_CHECK(ids[k].scalar_type() == torch::kInt32 && ids[k].is_contiguous(), "adagrad ids: int32 [nmax]");
+    TORCH_CHECK(ids[k].numel() < (1LL << 31), "adagrad ids: too many lookups");
+    TORCH_CHECK(g[k].scalar_type() == torch::kFloat32 && g[k].is_contiguous() &&
+                    g[k].numel() >= ids[k].numel() * W[k].size(1),
+                "adagrad g: fp32 [nmax, D]");
+    TORCH_CHECK(count[k].scalar_type() == torch::kInt32 && count[k].numel() >= 1, "adagrad count: int32 [1]");
+    TORCH_CHECK(slot[k].scalar_type() == torch::kInt32 && slot[k].is_contiguous() && slot[k].numel() >= W[k].size(0),
+                "adagrad slot: int32 [rows]");
+    pw.push_back(W[k].data_ptr<float>());
+    ph.push_back(H[k].data_ptr<float>());
+    D.push_back((int)W[k].size(1));
+    nmax.push_back((int)ids[k].numel());
+    pi.push_back(ids[k].data_ptr<int>());
+    pg.push_back(g[k].data_ptr<float>());
+    pn.push_back(count[k].data_ptr<int>());
+    ps.push_back(slot[k].data_ptr<int>());
+  }
+  fm_emb_adagrad_apply((int)n, pw.data(), ph.data(), D.data(), pi.data(), pg.data(), pn.data(), ps.data(), nmax.data(),
+                       lr.data_ptr<float>(), (float)eps, cur());
+}
+
 // dst[to + sum i_k ts_k] (+)= src[so + sum i_k ss_k] over the box d[4] (element offsets / strides
 // into the two buffers' storage; same dtype, bf16 or fp32)
 void strided_copy4(torch::Tensor src, torch::Tensor dst, std::vector<int64_t> d, std::vector<int64_t> ss,
@@ -659,6 +711,15 @@ void adam(torch::Tensor W, torch::Tensor G, torch::Tensor M, torch::Tensor V, c1
   TORCH_CHECK(alpha_t.scalar_type() == torch::kFloat32 && alpha_t.is_cuda(), "alpha_t: fp32 device scalar");
   fm_adam_update(W.data_ptr<float>(), G.data_ptr<float>(), M.data_ptr<float>(), V.data_ptr<float>(), (unsigned short*)mptr(Wc),
                  W.numel(), alpha_t.data_ptr<float>(), (float)b1, (float)b2, (float)wd, (float)eps, zero_grad ? 1 : 0, cur());
+}
+
+void adagrad(torch::Tensor W, torch::Tensor G, torch::Tensor H, c10::optional<torch::Tensor> Wc, torch::Tensor lr, double wd,
+             double eps, bool zero_grad) {
+  TORCH_CHECK(W.numel() == G.numel() && W.numel() == H.numel(), "adagrad: size mismatch");
+  TORCH_CHECK(lr.scalar_type() == torch::kFloat32 && lr.is_cuda(), "lr: fp32 device scalar");
+  TORCH_CHECK(!Wc.has_value() || !Wc->defined() || Wc->numel() == W.numel(), "adagrad: mirror size mismatch");
+  fm_adagrad_update(W.data_ptr<float>(), G.data_ptr<float>(), H.data_ptr<float>(), (unsigned short*)mptr(Wc),
+                    lr.data_ptr<float>(), W.numel(), (float)wd, (float)eps, zero_grad ? 1 : 0, cur());
 }
 
 void cast_bf16(torch::Tensor src, torch::Tensor dst) { fm_cast_bf16(src.data_ptr<float>(), (unsigned short*)dst.data_ptr(), src.numel(), cur()); }
@@ -1287,11 +1348,13 @@ PYBIND11_MODULE(_C, m) {
   m.def("strided_copy4", &strided_copy4);
   m.def("sdp_coalesce", &sdp_coalesce);
   m.def("sdp_apply", &sdp_apply);
+  m.def("emb_adagrad_apply", &emb_adagrad_apply);
   m.def("dot_fwd", &dot_fwd);
   m.def("dot_bwd", &dot_bwd, py::arg("zs"), py::arg("ldz"), py::arg("dout"), py::arg("ldo"), py::arg("dzs"),
         py::arg("lddz"), py::arg("acc_mask"), py::arg("D"), py::arg("self"), py::arg("act0") = 10);
   m.def("sgd", &sgd);
   m.def("adam", &adam);
+  m.def("adagrad", &adagrad);
   m.def("cast_bf16", &cast_bf16);
   m.def("loss", &loss, py::arg("loss_type"), py::arg("logits"), py::arg("labels"), py::arg("grad"), py::arg("scale"),
         py::arg("acc"), py::arg("mask"), py::arg("clamp_t") = 0.0);

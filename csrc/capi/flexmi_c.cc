@@ -482,6 +482,11 @@ int flexmi_model_set_adam_optimizer(flexmi_model_t m, flexmi_optimizer_t o) {
   return call_status(m->o, "set_adam_optimizer", PyTuple_Pack(1, o->o));
 }
 
+int flexmi_model_set_adagrad_optimizer(flexmi_model_t m, flexmi_optimizer_t o) {
+  Gil g;
+  return call_status(m->o, "set_adagrad_optimizer", PyTuple_Pack(1, o->o));
+}
+
 flexmi_tensor_t flexmi_model_get_label_tensor(flexmi_model_t m) {
   Gil g;
   return wrap<flexmi_tensor_s>(call(m->o, "get_label_tensor", PyTuple_New(0)));
@@ -845,6 +850,17 @@ flexmi_optimizer_t flexmi_adam_optimizer_create(flexmi_model_t m, double alpha, 
   return wrap<flexmi_optimizer_s>(o);
 }
 
+// element-wise Adagrad (torch.optim.Adagrad with lr_decay = 0); h0 = initial accumulator value
+flexmi_optimizer_t flexmi_adagrad_optimizer_create(flexmi_model_t m, double lr, double eps, double wd, double h0) {
+  Gil g;
+  PyObject* cls = attr("flexmi.core", "AdagradOptimizer");
+  if (!cls) return nullptr;
+  PyObject* o = PyObject_Call(cls, Py_BuildValue("(Odddd)", m->o, lr, eps, wd, h0), nullptr);
+  Py_DECREF(cls);
+  if (!o) capture_error("AdagradOptimizer");
+  return wrap<flexmi_optimizer_s>(o);
+}
+
 int flexmi_optimizer_set_lr(flexmi_optimizer_t o, double lr) {
   Gil g;
   return call_status(o->o, "set_learning_rate", Py_BuildValue("(d)", lr));
@@ -960,6 +976,8 @@ void flexmi_sgd_optimizer_destroy(flexmi_optimizer_t o) { flexmi_optimizer_destr
 int flexmi_sgd_optimizer_set_lr(flexmi_optimizer_t o, double lr) { return flexmi_optimizer_set_lr(o, lr); }
 void flexmi_adam_optimizer_destroy(flexmi_optimizer_t o) { flexmi_optimizer_destroy(o); }
 int flexmi_adam_optimizer_set_lr(flexmi_optimizer_t o, double lr) { return flexmi_optimizer_set_lr(o, lr); }
+void flexmi_adagrad_optimizer_destroy(flexmi_optimizer_t o) { flexmi_optimizer_destroy(o); }
+int flexmi_adagrad_optimizer_set_lr(flexmi_optimizer_t o, double lr) { return flexmi_optimizer_set_lr(o, lr); }
 flexmi_initializer_t flexmi_initializer_create_null(void) {
   Gil g;
   Py_INCREF(Py_None);

@@ -72,6 +72,7 @@ int flexmi_model_prefetch(flexmi_model_t m);
 int flexmi_model_print_layers(flexmi_model_t m, int id);
 int flexmi_model_set_sgd_optimizer(flexmi_model_t m, flexmi_optimizer_t opt);
 int flexmi_model_set_adam_optimizer(flexmi_model_t m, flexmi_optimizer_t opt);
+int flexmi_model_set_adagrad_optimizer(flexmi_model_t m, flexmi_optimizer_t opt);
 flexmi_tensor_t flexmi_model_get_label_tensor(flexmi_model_t m);
 flexmi_op_t flexmi_model_get_layer_by_id(flexmi_model_t m, int id);
 flexmi_parameter_t flexmi_model_get_parameter_by_id(flexmi_model_t m, int id);
@@ -147,6 +148,9 @@ flexmi_optimizer_t flexmi_sgd_optimizer_create(flexmi_model_t m, double lr, doub
                                                double weight_decay);
 flexmi_optimizer_t flexmi_adam_optimizer_create(flexmi_model_t m, double alpha, double beta1, double beta2,
                                                 double weight_decay, double epsilon);
+/* element-wise Adagrad (flexmi extension; torch.optim.Adagrad with lr_decay = 0) */
+flexmi_optimizer_t flexmi_adagrad_optimizer_create(flexmi_model_t m, double lr, double epsilon, double weight_decay,
+                                                   double initial_accumulator_value);
 int flexmi_optimizer_set_lr(flexmi_optimizer_t o, double lr);
 void flexmi_optimizer_destroy(flexmi_optimizer_t o);
 flexmi_initializer_t flexmi_glorot_uniform_initializer_create(int seed);
@@ -179,6 +183,8 @@ void flexmi_sgd_optimizer_destroy(flexmi_optimizer_t o);
 int flexmi_sgd_optimizer_set_lr(flexmi_optimizer_t o, double lr);
 void flexmi_adam_optimizer_destroy(flexmi_optimizer_t o);
 int flexmi_adam_optimizer_set_lr(flexmi_optimizer_t o, double lr);
+void flexmi_adagrad_optimizer_destroy(flexmi_optimizer_t o);
+int flexmi_adagrad_optimizer_set_lr(flexmi_optimizer_t o, double lr);
 flexmi_initializer_t flexmi_initializer_create_null(void); /* "no initializer": the op's default */
 void flexmi_glorot_uniform_initializer_destroy(flexmi_initializer_t i);
 void flexmi_zero_initializer_destroy(flexmi_initializer_t i);

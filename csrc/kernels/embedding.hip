@@ -19,6 +19,9 @@
 //     same few addresses, which L2 serialises; each wave accumulates into a PRIVATE LDS copy of the
 //     table gradient with plain read-add-write (row index wave-uniform, lane = column: 64 distinct
 //     banks, no atomics), the block sums its waves' copies and flushes one atomic per (row, col).
+// Backward under Adagrad (tables that are not replicated): the sparse-DP coalesce (claim / assign /
+// dups) sums the duplicate lookups of a row, then fm_emb_adagrad_apply updates the accumulator and
+// the weights of the touched rows only -- see "fused sparse Adagrad" below.
 #include "common.h"
 
 #include <algorithm>
@@ -655,6 +658,98 @@ __global__ void fm_sdp_reset_counts(SdpApplySet s) {
   if (threadIdx.x < s.n && s.t[threadIdx.x].own_count) *s.t[threadIdx.x].own_count = 0;
 }
 
+// ---- fused sparse Adagrad for non-replicated tables ---------------------------------------------
+// The coalesce above (claim / assign / dups) leaves one payload per table: count unique local rows
+// ids[u] with their summed gradients g[u].  Element-wise Adagrad of the touched rows only,
+//   H[r] += g g;  W[r] -= lr g / (sqrt(H[r]) + eps)      (r = ids[u], u < count),
+// equals dense Adagrad: an untouched row has gradient 0 and keeps H and W (no weight decay here).
+// Rows are unique within a payload, so H and W take plain read-modify-writes, no atomics.  The
+// count is read on the device (no host sync; capturable).  D % 4 == 0: D/4 lanes per row with
+// 16-B accesses (D = 128: 32 lanes, two rows per wave) and two rows in flight per lane -- the
+// second one's address is clamped to the last payload row and only its stores are predicated, so
+// the loads of an iteration stay unconditional.  Other D: one wave per row, lane = column.
+// (Row-wise Adagrad -- one accumulator per row -- is a different optimizer and not provided.)
+struct AdaDesc {
+  float* W;           // [rows][D] table shard
+  float* H;           // [rows][D] accumulator, same shape
+  const int* ids;     // [nmax] unique local rows      (payload)
+  const float* g;     // [nmax][D] summed gradients   (payload)
+  int* count;         // [1] unique rows; zeroed by fm_emb_adagrad_reset after the apply
+  int* slot;          // [rows] claim slots, freed (-1) here
+  int D, nmax, vec;
+};
+struct AdaSet {
+  AdaDesc t[MAXT];
+  int n;
+};
+
+__global__ void __launch_bounds__(256) fm_emb_adagrad_apply_multi(AdaSet s, const float* __restrict__ lr_p, float eps) {
+  const AdaDesc& d = s.t[blockIdx.y];
+  const long cnt = min(*d.count, d.nmax);
+  if (cnt <= 0) return;
+  const float lr = lr_p[0];
+  if (d.vec) {
+    const int D4 = d.D >> 2;
+    const int lpr = D4 < 64 ? D4 : 64;
+    const int rpi = 256 / lpr;
+    const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
+    if (sub >= rpi) return;
+    const long stride = (long)gridDim.x * rpi;
+    for (long u0 = (long)blockIdx.x * rpi + sub; u0 < cnt; u0 += 2 * stride) {
+      const bool live1 = u0 + stride < cnt;            // uniform across the row's lanes
+      const long u1 = live1 ? u0 + stride : cnt - 1;
+      const long r0 = d.ids[u0], r1 = d.ids[u1];
+      for (int c4 = lc; c4 < D4; c4 += lpr) {
+        const int c = c4 * 4;
+        f32x4_t* hp0 = reinterpret_cast<f32x4_t*>(d.H + r0 * d.D + c);
+        f32x4_t* wp0 = reinterpret_cast<f32x4_t*>(d.W + r0 * d.D + c);
+        f32x4_t* hp1 = reinterpret_cast<f32x4_t*>(d.H + r1 * d.D + c);
+        f32x4_t* wp1 = reinterpret_cast<f32x4_t*>(d.W + r1 * d.D + c);
+        const f32x4_t g0 = *reinterpret_cast<const f32x4_t*>(d.g + u0 * d.D + c);
+        const f32x4_t g1 = *reinterpret_cast<const f32x4_t*>(d.g + u1 * d.D + c);
+        f32x4_t h0 = *hp0, h1 = *hp1, w0 = *wp0, w1 = *wp1;
+        h0 += g0 * g0;
+        h1 += g1 * g1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          w0[j] -= lr * g0[j] / (sqrtf(h0[j]) + eps);
+          w1[j] -= lr * g1[j] / (sqrtf(h1[j]) + eps);
+        }
+        *hp0 = h0;
+        *wp0 = w0;
+        if (live1) {
+          *hp1 = h1;
+          *wp1 = w1;
+        }
+      }
+      if (lc == 0) {
+        d.slot[r0] = -1;                               // release the claims for the next step
+        if (live1) d.slot[r1] = -1;
+      }
+    }
+  } else {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (long u = blockIdx.x * 4L + wave; u < cnt; u += (long)gridDim.x * 4) {
+      const long r = d.ids[u];
+      float* h = d.H + r * d.D;
+      float* w = d.W + r * d.D;
+      const float* gu = d.g + u * d.D;
+      for (int c = lane; c < d.D; c += 64) {
+        const float g = gu[c];
+        const float hc = h[c] + g * g;
+        h[c] = hc;
+        w[c] -= lr * g / (sqrtf(hc) + eps);
+      }
+      if (lane == 0) d.slot[r] = -1;
+    }
+  }
+}
+
+// zero the counts once the apply has read them (a separate tiny launch, as fm_sdp_reset_counts)
+__global__ void fm_emb_adagrad_reset(AdaSet s) {
+  if (threadIdx.x < s.n) *s.t[threadIdx.x].count = 0;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -854,5 +949,30 @@ extern "C" void fm_sdp_apply_segments(int n, int segs, int own_seg, float* const
       if (sg == own_seg) last = s;
     }
     if (own_seg >= 0 && own_seg < segs) hipLaunchKernelGGL(fm_sdp_reset_counts, dim3(1), dim3(64), 0, st, last);
+  }
+}
+
+// ---- sparse Adagrad launcher -----------------------------------------------------------------
+// one payload (ids, g, count) per table from fm_sdp_coalesce -> H / W row updates, slots freed,
+// counts zeroed; nmax[k] = capacity of table k's payload (lookups per step)
+extern "C" void fm_emb_adagrad_apply(int n, float* const* W, float* const* H, const int* D, const int* const* ids,
+                                     const float* const* g, int* const* count, int* const* slot, const int* nmax,
+                                     const float* lr, float eps, hipStream_t st) {
+  if (n <= 0) return;
+  for (size_t base = 0; base < (size_t)n; base += MAXT) {
+    const int m = (int)std::min<size_t>(MAXT, n - base);
+    AdaSet s;
+    int nm = 1;
+    for (int i = 0; i < m; ++i) {
+      const int k = (int)base + i;
+      const bool vec = D[k] % 4 == 0 && ((((uintptr_t)W[k]) | ((uintptr_t)H[k]) | ((uintptr_t)g[k])) & 15) == 0;
+      s.t[i] = AdaDesc{W[k], H[k], ids[k], g[k], count[k], slot[k], D[k], nmax[k], vec ? 1 : 0};
+      nm = std::max(nm, nmax[k]);
+    }
+    s.n = m;
+    // >= 4 rows per block-iteration in either form, two in flight per lane in the vector form
+    dim3 grid((unsigned)std::max(1, std::min((nm + 7) / 8, 2048)), m);
+    hipLaunchKernelGGL(fm_emb_adagrad_apply_multi, grid, dim3(256), 0, st, s, lr, eps);
+    hipLaunchKernelGGL(fm_emb_adagrad_reset, dim3(1), dim3(64), 0, st, s);
   }
 }

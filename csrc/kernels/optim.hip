@@ -2,7 +2,7 @@
 // tasks of src/runtime/optimizer_kernel.cu:23-41 sgd_update and :134-154 adam_update, and the
 // gradient-replica sums of :96-101 / :220-225 which RCCL all-reduce now does).
 // ONE launch updates every parameter shard of the rank: fp32 master weights, optional momentum /
-// Adam state, and the bf16 compute mirror written in the same pass (no separate cast kernel).
+// Adam / Adagrad state, and the bf16 compute mirror written in the same pass (no separate cast kernel).
 // Vectorised 16-B loads/stores; lr is read from device memory so the step is graph-capturable.
 #include "common.h"
 
@@ -117,6 +117,45 @@ __global__ void fm_adam_kernel(float* __restrict__ W, float* __restrict__ G, flo
   }
 }
 
+// Adagrad (torch.optim.Adagrad with lr_decay = 0): g = G + wd W; H += g g; W -= lr g / (sqrt(H) + eps).
+// Scalar head up to the first 16-B boundary of W (vec: G, H and the bf16 mirror share that
+// boundary), 16-B vector body, scalar tail; vec == 0 runs every element through the scalar form.
+__global__ void fm_adagrad_kernel(float* __restrict__ W, float* __restrict__ G, float* __restrict__ H,
+                                  unsigned short* __restrict__ Wc, const float* __restrict__ lr_p, long n, long head,
+                                  float wd, float eps, int vec, int zero_g) {
+  const float lr = lr_p[0];
+  const long n4 = vec ? (n - head) / 4 : 0;
+  const long stride = (long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  auto one = [&](long i) {
+    float w = W[i];
+    const float g = G[i] + wd * w;
+    if (zero_g) G[i] = 0.f;
+    const float h = H[i] + g * g;
+    H[i] = h;
+    w -= lr * g / (sqrtf(h) + eps);
+    W[i] = w;
+    if (Wc) Wc[i] = f2bf(w);
+  };
+  for (long i = t0; i < head; i += stride) one(i);
+  for (long i = t0; i < n4; i += stride) {
+    const long e = head + 4 * i;
+    f32x4_t w = *reinterpret_cast<const f32x4_t*>(W + e);
+    const f32x4_t g = *reinterpret_cast<const f32x4_t*>(G + e) + wd * w;
+    f32x4_t h = *reinterpret_cast<const f32x4_t*>(H + e) + g * g;
+    if (zero_g) *reinterpret_cast<f32x4_t*>(G + e) = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4_t*>(H + e) = h;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] -= lr * g[j] / (sqrtf(h[j]) + eps);
+    *reinterpret_cast<f32x4_t*>(W + e) = w;
+    if (Wc) {
+      bf16x4_t c;
+      c[0] = (short)f2bf(w[0]); c[1] = (short)f2bf(w[1]); c[2] = (short)f2bf(w[2]); c[3] = (short)f2bf(w[3]);
+      *reinterpret_cast<bf16x4_t*>(Wc + e) = c;
+    }
+  }
+  for (long i = head + 4 * n4 + t0; i < n; i += stride) one(i);
+}
+
 __global__ void fm_cast_bf16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, long n) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) dst[i] = f2bf(src[i]);
 }
@@ -156,6 +195,18 @@ extern "C" void fm_adam_update(float* W, float* G, float* M, float* V, unsigned 
   if (n <= 0) return;
   hipLaunchKernelGGL(fm_adam_kernel, dim3(fm_grid(n)), dim3(256), 0, s, W, G, M, V, Wc, n, alpha_t, b1, b2, wd, eps,
                      zero_g);
+}
+
+extern "C" void fm_adagrad_update(float* W, float* G, float* H, unsigned short* Wc, const float* lr, long n, float wd,
+                                  float eps, int zero_g, hipStream_t s) {
+  if (n <= 0) return;
+  long head = (long)((16 - (((uintptr_t)W) & 15)) & 15) / 4;
+  if (head > n) head = n;
+  const bool al = (((uintptr_t)W) & 3) == 0 && ((((uintptr_t)(W + head)) | ((uintptr_t)(G + head)) | ((uintptr_t)(H + head))) & 15) == 0 &&
+                  (!Wc || (((uintptr_t)(Wc + head)) & 7) == 0);
+  if (!al) head = 0;
+  hipLaunchKernelGGL(fm_adagrad_kernel, dim3(fm_grid(al ? n / 4 + 1 : n)), dim3(256), 0, s, W, G, H, Wc, lr, n, head, wd,
+                     eps, al ? 1 : 0, zero_g);
 }
 
 extern "C" void fm_cast_bf16(const float* src, unsigned short* dst, long n, hipStream_t s) {

@@ -41,8 +41,8 @@ def dlrm_hetero_strategy(num_emb):
     return s
 
 
-def _model(name, gpus, batch, small):
-    from flexmi.core import FFConfig, FFModel, SGDOptimizer
+def _model(name, gpus, batch, small, optimizer="sgd"):
+    from flexmi.core import AdagradOptimizer, AdamOptimizer, FFConfig, FFModel, SGDOptimizer
     from flexmi.models import zoo
     cfg = FFConfig()
     cfg.device = "cpu"
@@ -50,7 +50,9 @@ def _model(name, gpus, batch, small):
     cfg.batchSize = batch
     m = FFModel(cfg)
     built = zoo.build(name, m, small=small)
-    m.optimizer = SGDOptimizer(m, built.lr)
+    # the optimizer decides how tables are priced: SGD and Adagrad update non-replicated tables
+    # sparsely, and only SGD trains replicated ones by sparse data parallelism
+    m.optimizer = {"sgd": SGDOptimizer, "adagrad": AdagradOptimizer, "adam": AdamOptimizer}[optimizer](m, built.lr)
     return m
 
 
@@ -73,6 +75,7 @@ def main(argv=None):
         p.add_argument("--gpus", type=int, default=8)
         p.add_argument("--batch", type=int, default=0, help="global batch (default 64 per GPU; DLRM 8192)")
         p.add_argument("--small", action="store_true")
+        p.add_argument("--optimizer", choices=["sgd", "adagrad", "adam"], default="sgd")
         p.add_argument("--strategy", help="strategy .pb (simulate) / initial state (search)")
         p.add_argument("--trace", help="write the predicted timeline as Chrome trace JSON")
         p.add_argument("--machine", help="machine model JSON override")
@@ -107,7 +110,7 @@ def main(argv=None):
     from flexmi.parallel.cost import CostModel
     from flexmi.parallel.search import SimGraph, optimize
     batch = a.batch or ((8192 if a.model.startswith("dlrm") else 64) * a.gpus)
-    m = _model(a.model, a.gpus, batch, a.small)
+    m = _model(a.model, a.gpus, batch, a.small, a.optimizer)
     mach = MachineModel.load(a.machine, a.gpus) if a.machine else MachineModel.mi355x(a.gpus)
     init = None
     if a.strategy:

@@ -295,6 +295,10 @@ class FFModel:
         self.optimizer = optimizer
         optimizer.model = self
 
+    def set_adagrad_optimizer(self, optimizer):
+        self.optimizer = optimizer
+        optimizer.model = self
+
     def compile(self, optimizer=None, loss_type=None, metrics=None, comp_mode=None):
         """``FFModel::compile`` (``src/runtime/model.cc:995-1080``)."""
         if optimizer is not None:

@@ -1,4 +1,4 @@
-"""SGD and Adam (``include/optimizer.h:26-74``, ``src/runtime/optimizer_kernel.cu``).
+"""SGD, Adam (``include/optimizer.h:26-74``, ``src/runtime/optimizer_kernel.cu``) and Adagrad.
 
 Reference: one single-point Legion task per parameter gathers every gradient replica to one GPU,
 sums them and applies the update (``optimizer_kernel.cu:44-110``).  flexmi: gradients are
@@ -10,6 +10,21 @@ Update rules are bit-for-bit the reference's:
   SGD : g = ∇ + wd·W; V = μV + g; g = nesterov ? g + μV : V (only if μ>0); W -= lr·g
   Adam: β1ᵗ,β2ᵗ updated in ``next()``; α_t = α·sqrt(1-β2ᵗ)/(1-β1ᵗ);
         g = ∇ + wd·W; m = β1 m + (1-β1) g; v = β2 v + (1-β2) g²; W -= α_t·m/(sqrt(v)+ε)
+
+Adagrad is a flexmi extension (the reference has none) with ``torch.optim.Adagrad``'s rule at
+``lr_decay = 0``:
+
+  Adagrad: g = ∇ + wd·W; H += g·g (H starts at ``initial_accumulator_value``); W -= lr·g/(sqrt(H)+ε)
+
+Sparse embedding updates (no dense gradient buffer) need the update of an untouched row to be
+the identity.  SGD without momentum / weight decay and Adagrad without weight decay qualify
+(``sparse_capable``): under Adagrad a non-replicated table keeps an accumulator ``h`` of its own
+shape and every step updates only the looked-up rows, duplicates summed BEFORE the gradient is
+squared (``csrc/kernels/embedding.hip`` fm_sdp_coalesce + fm_emb_adagrad_apply) -- equal to dense
+Adagrad.  Replicated tables under Adagrad take the dense path (``sparse_dp_capable`` is False:
+applying the replicas' segments one by one is not Adagrad of the summed gradient).  Not provided:
+row-wise Adagrad (one accumulator per row), host-placed tables under Adagrad, ``lr_decay``, and
+Adagrad in the native C++ engine.
 """
 from __future__ import annotations
 
@@ -27,6 +42,14 @@ class Optimizer:
 
     def state_names(self):
         return []
+
+    def state_init(self, name):
+        """Initial value of every element of the state buffer ``name`` (the executor fills the
+        dense groups, the ZeRO shards and the sparse tables' state with it)."""
+        return 0.0
+
+    # replicated tables trained by touched-row exchange (Embedding.sdp_*): an SGD form only
+    sparse_dp_capable = False
 
     def state_dict(self):
         return {}
@@ -56,6 +79,10 @@ class SGDOptimizer(Optimizer):
         """Embedding rows can be updated in place (no dense grad) iff the update of an
         untouched row is the identity: no weight decay, no momentum."""
         return self.momentum == 0.0 and self.weight_decay == 0.0
+
+    @property
+    def sparse_dp_capable(self):
+        return self.sparse_capable
 
     def update_torch(self, w, g, state):
         gt = g + self.weight_decay * w
@@ -115,3 +142,47 @@ class AdamOptimizer(Optimizer):
     def load_state_dict(self, d):
         for k, v in d.items():
             setattr(self, k, v)
+
+
+class AdagradOptimizer(Optimizer):
+    """Element-wise Adagrad, ``torch.optim.Adagrad`` with ``lr_decay = 0``."""
+
+    def __init__(self, ffmodel=None, lr=0.01, epsilon=1e-10, weight_decay=0.0, initial_accumulator_value=0.0):
+        super().__init__(ffmodel)
+        self.lr = float(lr)
+        self.epsilon = float(epsilon)
+        self.weight_decay = float(weight_decay)
+        self.initial_accumulator_value = float(initial_accumulator_value)
+        if self.initial_accumulator_value < 0:
+            raise ValueError("initial_accumulator_value must be >= 0")
+
+    def set_learning_rate(self, learning_rate):
+        self.lr = float(learning_rate)
+        if self.model is not None and getattr(self.model, "executor", None) is not None:
+            self.model.executor.set_lr(self.lr)
+
+    def state_names(self):
+        return ["h"]
+
+    def state_init(self, name):
+        return self.initial_accumulator_value
+
+    @property
+    def sparse_capable(self):
+        """A row no lookup touched has gradient 0 and keeps H and W iff there is no weight decay."""
+        return self.weight_decay == 0.0
+
+    # replicated tables stay dense: the replica all-reduce sums the gradients before they are squared
+    sparse_dp_capable = False
+
+    def update_torch(self, w, g, state):
+        gt = g + self.weight_decay * w
+        h = state["h"]
+        h.addcmul_(gt, gt)
+        w.sub_(self.lr * gt / (h.sqrt() + self.epsilon))
+
+    def state_dict(self):
+        return {"lr": self.lr}
+
+    def load_state_dict(self, d):
+        self.lr = d.get("lr", self.lr)

@@ -1,5 +1,5 @@
-"""Keras optimizers (``python/flexflow/keras/optimizers.py``) over flexmi's SGD / Adam."""
-from flexmi.core.optimizers import AdamOptimizer, SGDOptimizer
+"""Keras optimizers (``python/flexflow/keras/optimizers.py``) over flexmi's SGD / Adam / Adagrad."""
+from flexmi.core.optimizers import AdagradOptimizer, AdamOptimizer, SGDOptimizer
 
 
 class Optimizer:
@@ -29,4 +29,16 @@ class Adam(Optimizer):
 
     def build(self, ffmodel):
         self.ff = AdamOptimizer(ffmodel, self.lr, self.b1, self.b2, self.weight_decay, self.eps)
+        return self.ff
+
+
+class Adagrad(Optimizer):
+    """``keras.optimizers.Adagrad`` (its defaults); element-wise accumulator, no ``lr_decay``."""
+
+    def __init__(self, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, weight_decay=0.0, **kw):
+        super().__init__()
+        self.lr, self.h0, self.eps, self.weight_decay = float(learning_rate), initial_accumulator_value, epsilon, weight_decay
+
+    def build(self, ffmodel):
+        self.ff = AdagradOptimizer(ffmodel, self.lr, self.eps, self.weight_decay, self.h0)
         return self.ff

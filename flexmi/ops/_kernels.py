@@ -328,6 +328,11 @@ def adam_update(master, grad, m, v, compute, alpha_t, b1, b2, wd, eps, zero_grad
     C().adam(master, grad, m, v, compute, alpha_t, b1, b2, wd, eps, zero_grad)
 
 
+def adagrad_update(master, grad, h, compute, lr_tensor, wd, eps, zero_grad=False):
+    """Element-wise Adagrad over a flat fp32 buffer (csrc/kernels/optim.hip fm_adagrad_update)."""
+    C().adagrad(master, grad, h, compute, lr_tensor, wd, eps, zero_grad)
+
+
 def loss_forward_backward(loss_type, logits, labels, grad, scale, acc, mask, clamp=0.0):
     """clamp in (0, 0.5): predictions clamped to [clamp, 1-clamp] (DLRM --loss-threshold)."""
     C().loss(loss_type, logits, labels, grad, scale, acc, mask, float(clamp))

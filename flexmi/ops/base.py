@@ -49,6 +49,7 @@ class OpCtx:
         self.in_grads: List[torch.Tensor] = []
         self.in_grad_accumulate: List[bool] = []
         self.weight_grads: List[torch.Tensor] = []
+        self.weight_state: List[dict] = []      # optimizer state per weight (sparse tables: {"h": ...})
         self.saved = {}
         self.training = True
         self.sparse_update = None   # callable(lr) for fused sparse optimizers (embeddings)

@@ -11,6 +11,9 @@ table).  The backward never materialises a dense gradient for SGD: rows are upda
 (W[idx] -= lr*dy).  Mostly-unique (large) tables use owner-computes: each row is claimed by one
 lookup (CAS), duplicates add with atomics, the owner applies a plain 16-B read-modify-write;
 other tables use 256-B-contiguous fp32 atomics; tiny tables accumulate in LDS first.
+Under Adagrad (no weight decay, table not replicated) the backward coalesces the lookups into
+(unique row, summed gradient) payloads and updates accumulator and weights of those rows only
+(``adagrad_group``); still no dense gradient, one extra table-sized buffer (the accumulator).
 SOAP: sample split, **column (parameter) split** of the table, whole-table placement
 (``dims=[1,1]``, device k) -- a 100 M-row table fits one MI355X's 288 GB of HBM -- and **row
 split** (flexmi extension of the strategy format: a third internal degree, ``dims=[c, n, r]``):
@@ -98,6 +101,21 @@ class SparseDPState:
         comm.all_gather(self.recv, self.send, self.holders)
 
 
+class SparseAdagradState(SparseDPState):
+    """Coalesce buffers of one Adagrad-trained table group: the single-holder form of the sparse-DP
+    payload (count, unique local rows, summed fp32 gradients per table; claim slots and compact ids
+    on the GPU).  No exchange: the payload is applied where it was packed."""
+
+    def __init__(self, ops, ctxs, rank):
+        super().__init__(ops, ctxs, (rank,), rank)
+        # the one segment is read where it was written (no all-gather copy)
+        self.recv = self.send
+        self.rcount, self.rids, self.rg = [self.count[0]], [self.ids[0]], [self.g[0]]
+
+    def exchange(self, comm):
+        pass
+
+
 class Embedding(Op):
     op_type = OperatorType.OP_EMBEDDING
     name_prefix = "Embed"
@@ -119,6 +137,9 @@ class Embedding(Op):
         # the replica set of a replicated table trained by touched-row exchange
         self.sparse_sgd = False
         self.sparse_dp = None
+        # sparse_adagrad = epsilon when the table is trained by the fused sparse Adagrad update
+        # (non-replicated tables; accumulator in ctx.weight_state[0]["h"]), else None
+        self.sparse_adagrad = None
 
     def splittable_dims(self):
         return {0, 1}
@@ -214,6 +235,9 @@ class Embedding(Op):
     def backward(self, ctx: OpCtx):
         idx = ctx.inputs[0]
         dy = ctx.out_grads[0]
+        if self.sparse_adagrad is not None:
+            Embedding.adagrad_group([self], [ctx])
+            return
         if self.sparse_sgd:
             # fused sparse SGD (no dense grad): W[idx] -= lr * dy  (duplicates summed first)
             scale = 1.0 / idx.shape[1] if self.aggr == AggrMode.AGGR_MODE_AVG else 1.0
@@ -252,6 +276,7 @@ class Embedding(Op):
     def can_group(a, b, ca, cb):
         """Executor fusion: independent embeddings with the same placement run as ONE launch."""
         return (ca.outputs[0].dtype == cb.outputs[0].dtype and a.sparse_sgd == b.sparse_sgd
+                and getattr(a, "sparse_adagrad", None) == getattr(b, "sparse_adagrad", None)
                 and getattr(a, "sparse_dp", None) == getattr(b, "sparse_dp", None)
                 and ca.inputs[0].shape[0] == cb.inputs[0].shape[0])
 
@@ -272,6 +297,9 @@ class Embedding(Op):
         if not ctxs[0].hip:
             for op, c in zip(ops, ctxs):
                 op.backward(c)
+            return
+        if ops[0].sparse_adagrad is not None:
+            Embedding.adagrad_group(ops, ctxs)
             return
         scales = [1.0 / c.inputs[0].shape[1] if op.aggr == AggrMode.AGGR_MODE_AVG else 1.0 for op, c in zip(ops, ctxs)]
         if ops[0].sparse_sgd:
@@ -312,8 +340,8 @@ class Embedding(Op):
         return st
 
     @staticmethod
-    def sdp_pack(ops, ctxs):
-        st = ctxs[0].saved["sdp"]
+    def sdp_pack(ops, ctxs, st=None):
+        st = st or ctxs[0].saved["sdp"]
         scales = [1.0 / c.inputs[0].shape[1] if op.aggr == AggrMode.AGGR_MODE_AVG else 1.0 for op, c in zip(ops, ctxs)]
         if ctxs[0].hip:
             K.C().sdp_coalesce([c.weights[0] for c in ctxs], [c.inputs[0] for c in ctxs], [c.out_grads[0] for c in ctxs],
@@ -351,6 +379,43 @@ class Embedding(Op):
                 if n:
                     D = w.shape[1]
                     w.index_add_(0, st.rids[s][k][:n].long(), mlr * st.rg[s][k][:n * D].view(n, D))
+
+    # ---------------------------------------------------------- fused sparse Adagrad
+    # Non-replicated tables under AdagradOptimizer (weight_decay == 0): coalesce the step's lookups
+    # into (unique local rows, summed gradients) -- duplicates are summed BEFORE the gradient is
+    # squared -- then update H and W of those rows only.  Untouched rows have gradient 0 and keep H
+    # and W, so this equals dense element-wise Adagrad without a table-sized gradient buffer.
+    # Replicated tables are not handled here (they stay dense); row-wise Adagrad is not provided.
+    @staticmethod
+    def adagrad_group(ops, ctxs):
+        c0 = ctxs[0]
+        st = c0.saved.get("adagrad")
+        if st is None:
+            st = c0.saved["adagrad"] = SparseAdagradState(ops, ctxs, c0.rank)
+        Embedding.sdp_pack(ops, ctxs, st)
+        Embedding.adagrad_apply(ops, ctxs, st)
+
+    @staticmethod
+    def adagrad_apply(ops, ctxs, st):
+        lr = ctxs[0].lr
+        H = [c.weight_state[0]["h"] for c in ctxs]
+        if ctxs[0].hip:
+            eps = {float(op.sparse_adagrad) for op in ops}
+            assert len(eps) == 1
+            K.C().emb_adagrad_apply([c.weights[0] for c in ctxs], H, st.ids[0], st.g[0], st.count[0], st.slot, lr,
+                                    eps.pop())
+            return
+        lrf = lr.to(torch.float32)
+        for k, (op, c) in enumerate(zip(ops, ctxs)):
+            w, h = c.weights[0], H[k]
+            n = int(st.count[0][k].item())
+            if n:
+                D = w.shape[1]
+                rows = st.ids[0][k][:n].long()
+                g = st.g[0][k][:n * D].view(n, D)
+                hr = h[rows] + g * g
+                h[rows] = hr
+                w[rows] = w[rows] - lrf * g / (hr.sqrt() + float(op.sparse_adagrad))
 
     CLAIM = True                 # owner-computes path for mostly-unique tables (tests may switch it)
     # owner-computes when rows exceed CLAIM_RATIO x lookups per step (few enough duplicates for the

@@ -140,6 +140,10 @@ class SimGraph:
         opt = model.optimizer
         self.nstates = len(opt.state_names()) if opt is not None and hasattr(opt, "state_names") else 0
         self.sparse_ok = bool(getattr(opt, "sparse_capable", False))
+        # sparse data parallelism (replicated tables by touched-row exchange) is an SGD form:
+        # applying the replica segments one by one is not Adagrad of the summed gradient, so a
+        # replicated table under Adagrad is priced dense, as the executor trains it
+        self.sparse_dp_ok = self.sparse_ok and bool(getattr(opt, "sparse_dp_capable", False))
         self.ops = list(model.layers)
         md = self.machine.native_dict()
         if not md["xchg_chunks"]:
@@ -196,6 +200,8 @@ class SimGraph:
                 h = lay.holders[p]
                 sparse = emb and self.sparse_ok
                 sdp_words = 0.0
+                if sparse and len(h) > 1 and not self.sparse_dp_ok:
+                    sparse = False
                 if sparse and len(h) > 1:
                     # the executor's per-table rule (Executor._sdp_pays): sparse DP only where the
                     # touched-row all-gather moves fewer bytes than the dense replica all-reduce
@@ -229,8 +235,9 @@ class SimGraph:
                         wsync.append((float(vol * 4), list(h)))
                 for d in h:
                     if sparse:
-                        # the table + (sparse DP) the R-slot receive buffer of the all-gather
-                        mem[d] = mem.get(d, 0.0) + vol * 4.0 + sdp_words * 4.0
+                        # the table + (sparse DP) the R-slot receive buffer of the all-gather +
+                        # one table-sized buffer per optimizer state (sparse Adagrad: h)
+                        mem[d] = mem.get(d, 0.0) + vol * 4.0 * (1 + self.nstates) + sdp_words * 4.0
                     else:
                         mem[d] = mem.get(d, 0.0) + vol * (4.0 + 4.0 + 2.0 + 4.0 * self.nstates)
                         upd_bytes[d] = upd_bytes.get(d, 0.0) + vol * 4.0

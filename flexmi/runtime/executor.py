@@ -10,7 +10,7 @@ compiles (graph, strategy, rank) into:
     distribution than the producer made -- including partial-sum reductions in backward;
   * flat fp32 master/grad/optimizer-state buffers per gradient-sync group with bf16 compute
     mirrors, bucketed for async RCCL all-reduce overlapped with backward;
-  * a fused sparse-SGD path for non-replicated embedding tables (no dense gradient).
+  * a fused sparse-SGD / sparse-Adagrad path for non-replicated embedding tables (no dense gradient).
 
 All buffers are allocated once, so the whole step can be captured in a hipGraph
 (``Executor.capture_step``) -- the analogue of Legion tracing (``dlrm.cc:178-185``).
@@ -28,7 +28,7 @@ import torch
 
 from flexmi.core.loss_metrics import NUM_SLOTS, PerfMetrics, loss_and_metrics_torch
 from flexmi.core.initializers import _native_cpu
-from flexmi.core.optimizers import AdamOptimizer, SGDOptimizer
+from flexmi.core.optimizers import AdagradOptimizer, AdamOptimizer, SGDOptimizer
 from flexmi.core.types import DataType, LossType, to_torch_dtype
 from flexmi.ops.base import OpCtx
 from flexmi.parallel.layout import Layout, ParallelConfig, ReshardPlan, box_intersect, box_volume
@@ -895,6 +895,7 @@ class Executor:
                 c.weights.append(e.master if e else None)
                 c.wcompute.append(e.compute if e else None)
                 c.weight_grads.append(e.grad if e else None)
+                c.weight_state.append(e.state if e else None)
                 c.w_boxes.append(e.box if e else None)
             c.lr = self.lr_tensor
             # a split whose extent does not divide the degree can leave this rank an empty output
@@ -1129,6 +1130,11 @@ class Executor:
         self.wentries: Dict[int, WeightEntry] = {}
         groups: "OrderedDict[tuple, SyncGroup]" = OrderedDict()
         sparse_ok = isinstance(self.optimizer, SGDOptimizer) and self.optimizer.sparse_capable
+        # Adagrad without weight decay: non-replicated tables are updated row by row with an
+        # accumulator of the table's shape (Embedding.adagrad_group); replicated tables stay in the
+        # dense groups (the replica all-reduce sums the gradients before they are squared -- sparse
+        # DP would not), and host-placed tables are not supported
+        adagrad_ok = isinstance(self.optimizer, AdagradOptimizer) and self.optimizer.sparse_capable
         for op in reversed(ops):  # backward order => buckets fill contiguously
             pc = self.pcs[op.guid]
             lays = op.weight_layouts(pc)
@@ -1155,6 +1161,16 @@ class Executor:
                     continue
                 if op.op_type == OperatorType.OP_EMBEDDING:
                     op.sparse_dp = None
+                    op.sparse_adagrad = None
+                    if adagrad_ok and lays[wi].replication() == 1:
+                        e.sparse = True
+                        op.sparse_sgd = False
+                        op.sparse_adagrad = self.optimizer.epsilon
+                        e.master = self._alloc(e.shape, torch.float32)
+                        e.compute = e.master
+                        e.state = {"h": torch.full(e.shape, self.optimizer.state_init("h"), dtype=torch.float32,
+                                                   device=self.device)}
+                        continue
                 if (op.op_type == OperatorType.OP_EMBEDDING and sparse_ok
                         and (lays[wi].replication() == 1 or (SPARSE_DP and self._sdp_pays(op, lays[wi])))):
                     # non-replicated: fused sparse SGD; replicated: sparse data parallelism
@@ -1198,8 +1214,8 @@ class Executor:
             g.compute = torch.zeros((g.numel,), dtype=self.cdtype, device=self.device) if mixed else g.master
             snames = self.optimizer.state_names() if self.optimizer else []
             # ZeRO-1: optimizer state exists only for this rank's shard of every bucket
-            g.state = {n: torch.zeros(g.shard_numel if g.zero else g.numel, dtype=torch.float32, device=self.device)
-                       for n in snames}
+            g.state = {n: torch.full((g.shard_numel if g.zero else g.numel,), self.optimizer.state_init(n),
+                                     dtype=torch.float32, device=self.device) for n in snames}
             if g.zero:
                 g.gshard = self._alloc((g.shard_numel,), torch.float32)
                 g.mshard = self._alloc((g.shard_numel,), torch.float32)
@@ -2191,6 +2207,9 @@ class Executor:
                 if isinstance(opt, SGDOptimizer):
                     K.sgd_update(g.master, g.gradbuf, g.state.get("v"), comp, self.lr_tensor, opt.weight_decay,
                                  opt.momentum, opt.nesterov, zero_grad=True)
+                elif isinstance(opt, AdagradOptimizer):
+                    K.adagrad_update(g.master, g.gradbuf, g.state["h"], comp, self.lr_tensor, opt.weight_decay,
+                                     opt.epsilon, zero_grad=True)
                 else:
                     K.adam_update(g.master, g.gradbuf, g.state["m"], g.state["v"], comp, self.adam_state[2:3],
                                   opt.beta1, opt.beta2, opt.weight_decay, opt.epsilon, zero_grad=True)
@@ -2202,6 +2221,11 @@ class Executor:
                         v.mul_(opt.momentum).add_(gt)
                         gt = gt + opt.momentum * v if opt.nesterov else v
                     g.master.sub_(self.lr_tensor * gt)
+                elif isinstance(opt, AdagradOptimizer):
+                    gt = g.gradbuf + opt.weight_decay * g.master
+                    h_ = g.state["h"]
+                    h_.addcmul_(gt, gt)
+                    g.master.sub_(self.lr_tensor * gt / (h_.sqrt() + opt.epsilon))
                 else:
                     gt = g.gradbuf + opt.weight_decay * g.master
                     m_, v_ = g.state["m"], g.state["v"]
@@ -2220,6 +2244,8 @@ class Executor:
         if self.backend == "hip":
             if isinstance(opt, SGDOptimizer):
                 K.sgd_update(m, gr, st.get("v"), None, self.lr_tensor, opt.weight_decay, opt.momentum, opt.nesterov)
+            elif isinstance(opt, AdagradOptimizer):
+                K.adagrad_update(m, gr, st["h"], None, self.lr_tensor, opt.weight_decay, opt.epsilon)
             else:
                 K.adam_update(m, gr, st["m"], st["v"], None, self.adam_state[2:3], opt.beta1, opt.beta2,
                               opt.weight_decay, opt.epsilon)
@@ -2230,6 +2256,11 @@ class Executor:
                 v.mul_(opt.momentum).add_(gt)
                 gt = gt + opt.momentum * v if opt.nesterov else v
             m.sub_(self.lr_tensor * gt)
+        elif isinstance(opt, AdagradOptimizer):
+            gt = gr + opt.weight_decay * m
+            h_ = st["h"]
+            h_.addcmul_(gt, gt)
+            m.sub_(self.lr_tensor * gt / (h_.sqrt() + opt.epsilon))
         else:
             gt = gr + opt.weight_decay * m
             m_, v_ = st["m"], st["v"]
@@ -2480,4 +2511,7 @@ class Executor:
             st = c.saved.get("sdp")
             if st is not None:
                 sdp += (st.send.numel() + st.recv.numel()) * 4 + sum(t.numel() * 4 for t in st.slot + st.cid)
-        return {"activations": n, "dense_params": w, "sparse_tables": sp, "sparse_dp_payload": sdp}
+        # optimizer state held per sparse table (Adagrad: h, the table's shape)
+        sst = sum(t.numel() * 4 for e in self.wentries.values() if e.sparse for t in e.state.values())
+        return {"activations": n, "dense_params": w, "sparse_tables": sp, "sparse_dp_payload": sdp,
+                "sparse_opt_state": sst}
