@@ -14,8 +14,10 @@ loop is the reference's (dlrm.cc:160-195): per epoch ``num_samples / batch`` ite
 next_batch / forward / zero_gradients / backward / update, traced with begin/end_trace(111),
 then ``ELAPSED TIME = ..., THROUGHPUT = ... samples/s``.  ``--preset`` (mlperf, run_random,
 criteo_kaggle, summit, summit_large, kaggle_day1, tiny) seeds the architecture flags.
-``--optimizer {sgd,adagrad}`` (flexmi extension, default sgd): Adagrad keeps one accumulator per
-table element and updates non-replicated tables sparsely (``flexmi/core/optimizers.py``).
+``--optimizer {sgd,adagrad,rowwise_adagrad}`` (flexmi extension, default sgd): Adagrad keeps one
+accumulator per table element and updates non-replicated tables sparsely; row-wise Adagrad keeps
+one per table ROW and trains every table sparsely, replicated ones included
+(``flexmi/core/optimizers.py``).
 """
 from __future__ import annotations
 
@@ -30,7 +32,8 @@ sys.path.insert(0, ROOT)
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     import torch
-    from flexmi.core import AdagradOptimizer, FFConfig, FFModel, LossType, MetricsType, SGDOptimizer
+    from flexmi.core import (AdagradOptimizer, FFConfig, FFModel, LossType, MetricsType, RowwiseAdagradOptimizer,
+                             SGDOptimizer)
     from flexmi.models.dlrm import DLRMConfig, HDF5DLRMData, SyntheticDLRMData, build_dlrm
     from flexmi.parallel.comm import init_distributed
 
@@ -45,8 +48,8 @@ def main(argv=None):
         k = argv.index("--optimizer")
         optname = argv[k + 1]
         del argv[k:k + 2]
-        if optname not in ("sgd", "adagrad"):
-            raise SystemExit(f"--optimizer {optname}: expected sgd or adagrad")
+        if optname not in ("sgd", "adagrad", "rowwise_adagrad"):
+            raise SystemExit(f"--optimizer {optname}: expected sgd, adagrad or rowwise_adagrad")
     dcfg = DLRMConfig.parse_args(["dlrm"] + argv, base)
     cfg = FFConfig()
     cfg.parse_args(["dlrm"] + argv)
@@ -57,7 +60,8 @@ def main(argv=None):
     model = FFModel(cfg)
     dense_in, sparse, out = build_dlrm(model, dcfg)
     loss = LossType.LOSS_BINARY_CROSSENTROPY if dcfg.loss == "bce" else LossType.LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE
-    opt = (AdagradOptimizer if optname == "adagrad" else SGDOptimizer)(model, cfg.learningRate)
+    opt = {"sgd": SGDOptimizer, "adagrad": AdagradOptimizer,
+           "rowwise_adagrad": RowwiseAdagradOptimizer}[optname](model, cfg.learningRate)
     model.compile(opt, loss,
                   [MetricsType.METRICS_ACCURACY, MetricsType.METRICS_MEAN_SQUARED_ERROR])
     ex = model.init_layers()

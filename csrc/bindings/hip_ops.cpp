@@ -69,6 +69,13 @@ void fm_sdp_apply_segments(int n, int segs, int own_seg, float* const* W, const 
 void fm_emb_adagrad_apply(int n, float* const* W, float* const* H, const int* D, const int* const* ids,
                           const float* const* g, int* const* count, int* const* slot, const int* nmax, const float* lr,
                           float eps, hipStream_t st);
+void fm_emb_rowwise_adagrad_apply(int n, float* const* W, float* const* h, const int* D, const int* const* ids,
+                                  const float* const* g, int* const* count, int* const* slot, const int* nmax,
+                                  const float* lr, float eps, hipStream_t st);
+void fm_sdp_rowwise_merge_segments(int n, int segs, const int* rows, const int* D, const int* const* seg_ids,
+                                   const float* const* seg_g, const int* const* seg_count, const int* const* own_ids,
+                                   int* const* own_count, int* const* slot, int* const* mids, float* const* mg,
+                                   int* const* mcount, const int* nmax, const int* mcap, hipStream_t st);
 void fm_strided_copy4_run(const void* src, void* dst, int bf16, const int* d, const long* ss, const long* ts, long so,
                           long to, int acc, hipStream_t st);
 void fm_dot_interaction_fwd(const void* const* z, int F, long ldz, void* out, long ldo, long B, int D, int W, int self,
@@ -618,6 +625,123 @@ void emb_adagrad_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> 
   }
   fm_emb_adagrad_apply((int)n, pw.data(), ph.data(), D.data(), pi.data(), pg.data(), pn.data(), ps.data(), nmax.data(),
                        lr.data_ptr<float>(), (float)eps, cur());
+}
+
+// fused sparse row-wise Adagrad (embedding.hip): one coalesced payload (ids, g, count) per table ->
+// h[ids] += mean(g g), W[ids] -= lr g / (sqrt(h[ids]) + eps); frees the slots and zeroes the counts.
+// H holds one fp32 per table row, shaped [rows, 1] (sliced by the checkpoint code like the table)
+void emb_rowwise_adagrad_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> H, std::vector<torch::Tensor> ids,
+                               std::vector<torch::Tensor> g, std::vector<torch::Tensor> count,
+                               std::vector<torch::Tensor> slot, torch::Tensor lr, double eps) {
+  const size_t n = W.size();
+  if (n == 0) return;
+  TORCH_CHECK(H.size() == n && ids.size() == n && g.size() == n && count.size() == n && slot.size() == n,
+              "emb_rowwise_adagrad_apply: one buffer of each kind per table");
+  check_cuda(lr, "lr");
+  TORCH_CHECK(lr.scalar_type() == torch::kFloat32 && lr.numel() >= 1, "lr: fp32 device scalar");
+  std::vector<float*> pw, ph;
+  std::vector<int> D, nmax;
+  std::vector<const int*> pi;
+  std::vector<const float*> pg;
+  std::vector<int*> pn, ps;
+  for (size_t k = 0; k < n; ++k) {
+    check_cuda(W[k], "W");
+    check_cuda(H[k], "H");
+    check_cuda(ids[k], "ids");
+    check_cuda(g[k], "g");
+    check_cuda(count[k], "count");
+    check_cuda(slot[k], "slot");
+    TORCH_CHECK(W[k].scalar_type() == torch::kFloat32 && W[k].is_contiguous() && W[k].dim() == 2, "tables fp32 [rows, D]");
+    TORCH_CHECK(H[k].scalar_type() == torch::kFloat32 && H[k].is_contiguous() && H[k].dim() == 2 &&
+                    H[k].size(0) == W[k].size(0) && H[k].size(1) == 1,
+                "rowwise adagrad H: fp32 [rows, 1]");
+    TORCH_CHECK(ids[k].scalar_type() == torch::kInt32 && ids[k].is_contiguous(), "rowwise adagrad ids: int32 [nmax]");
+    TORCH_CHECK(ids[k].numel() < (1LL << 31), "rowwise adagrad ids: too many lookups");
+    TORCH_CHECK(g[k].scalar_type() == torch::kFloat32 && g[k].is_contiguous() &&
+                    g[k].numel() >= ids[k].numel() * W[k].size(1),
+                "rowwise adagrad g: fp32 [nmax, D]");
+    TORCH_CHECK(count[k].scalar_type() == torch::kInt32 && count[k].numel() >= 1, "rowwise adagrad count: int32 [1]");
+    TORCH_CHECK(slot[k].scalar_type() == torch::kInt32 && slot[k].is_contiguous() && slot[k].numel() >= W[k].size(0),
+                "rowwise adagrad slot: int32 [rows]");
+    pw.push_back(W[k].data_ptr<float>());
+    ph.push_back(H[k].data_ptr<float>());
+    D.push_back((int)W[k].size(1));
+    nmax.push_back((int)ids[k].numel());
+    pi.push_back(ids[k].data_ptr<int>());
+    pg.push_back(g[k].data_ptr<float>());
+    pn.push_back(count[k].data_ptr<int>());
+    ps.push_back(slot[k].data_ptr<int>());
+  }
+  fm_emb_rowwise_adagrad_apply((int)n, pw.data(), ph.data(), D.data(), pi.data(), pg.data(), pn.data(), ps.data(),
+                               nmax.data(), lr.data_ptr<float>(), (float)eps, cur());
+}
+
+// replicated tables under row-wise Adagrad: free the own claims (own_ids / own_count, zeroed), then
+// merge the gathered segments (segs x n payloads, segment-major) in order into (mids, mg, mcount);
+// rows[k] = rows of table k's shard (= slot[k] entries)
+void sdp_rowwise_merge(std::vector<torch::Tensor> seg_ids, std::vector<torch::Tensor> seg_g,
+                       std::vector<torch::Tensor> seg_count, std::vector<torch::Tensor> own_ids,
+                       std::vector<torch::Tensor> own_count, std::vector<torch::Tensor> slot,
+                       std::vector<torch::Tensor> mids, std::vector<torch::Tensor> mg, std::vector<torch::Tensor> mcount,
+                       std::vector<int64_t> Ds, int64_t segs) {
+  const size_t n = slot.size();
+  if (n == 0) return;
+  TORCH_CHECK(segs >= 1 && seg_ids.size() == n * segs && seg_g.size() == n * segs && seg_count.size() == n * segs,
+              "sdp_rowwise_merge: segs x tables payload views");
+  TORCH_CHECK(own_ids.size() == n && own_count.size() == n && mids.size() == n && mg.size() == n && mcount.size() == n &&
+                  Ds.size() == n,
+              "sdp_rowwise_merge: one buffer of each kind per table");
+  std::vector<int> rows, D, nmax, mcap;
+  std::vector<const int*> pi, pn, poi;
+  std::vector<const float*> pg;
+  std::vector<int*> ps, po, pmi, pmc;
+  std::vector<float*> pmg;
+  auto i32 = [](const torch::Tensor& t, const char* what) {
+    check_cuda(t, what);
+    TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.is_contiguous(), what, ": contiguous int32");
+  };
+  for (size_t k = 0; k < n; ++k) {
+    i32(slot[k], "merge slot");
+    i32(own_ids[k], "merge own ids");
+    i32(own_count[k], "merge own count");
+    i32(mids[k], "merge mids");
+    i32(mcount[k], "merge mcount");
+    check_cuda(mg[k], "merge mg");
+    TORCH_CHECK(Ds[k] >= 1 && slot[k].numel() >= 1 && slot[k].numel() < (1LL << 31), "sdp_rowwise_merge: table shape");
+    TORCH_CHECK(own_count[k].numel() >= 1 && mcount[k].numel() >= 1, "sdp_rowwise_merge: counts int32 [1]");
+    TORCH_CHECK(own_ids[k].numel() < (1LL << 31) && mids[k].numel() >= 1 && mids[k].numel() < (1LL << 31),
+                "sdp_rowwise_merge: payload capacity");
+    // every unique row of the segments needs a merged entry
+    TORCH_CHECK(mids[k].numel() >= std::min<int64_t>(slot[k].numel(), segs * own_ids[k].numel()),
+                "sdp_rowwise_merge: merged capacity below min(rows, segs * nmax)");
+    TORCH_CHECK(mg[k].scalar_type() == torch::kFloat32 && mg[k].is_contiguous() &&
+                    mg[k].numel() >= mids[k].numel() * Ds[k],
+                "sdp_rowwise_merge mg: fp32 [mcap, D]");
+    rows.push_back((int)slot[k].numel());
+    D.push_back((int)Ds[k]);
+    nmax.push_back((int)own_ids[k].numel());
+    mcap.push_back((int)mids[k].numel());
+    ps.push_back(slot[k].data_ptr<int>());
+    poi.push_back(own_ids[k].data_ptr<int>());
+    po.push_back(own_count[k].data_ptr<int>());
+    pmi.push_back(mids[k].data_ptr<int>());
+    pmc.push_back(mcount[k].data_ptr<int>());
+    pmg.push_back(mg[k].data_ptr<float>());
+  }
+  for (size_t j = 0; j < n * segs; ++j) {
+    const size_t k = j % n;
+    i32(seg_ids[j], "merge segment ids");
+    i32(seg_count[j], "merge segment count");
+    check_cuda(seg_g[j], "merge segment g");
+    TORCH_CHECK(seg_ids[j].numel() == nmax[k] && seg_count[j].numel() >= 1 && seg_g[j].scalar_type() == torch::kFloat32 &&
+                    seg_g[j].is_contiguous() && seg_g[j].numel() >= (int64_t)nmax[k] * D[k],
+                "sdp_rowwise_merge: payload sizes");
+    pi.push_back(seg_ids[j].data_ptr<int>());
+    pg.push_back(seg_g[j].data_ptr<float>());
+    pn.push_back(seg_count[j].data_ptr<int>());
+  }
+  fm_sdp_rowwise_merge_segments((int)n, (int)segs, rows.data(), D.data(), pi.data(), pg.data(), pn.data(), poi.data(),
+                                po.data(), ps.data(), pmi.data(), pmg.data(), pmc.data(), nmax.data(), mcap.data(), cur());
 }
 
 // dst[to + sum i_k ts_k] (+)= src[so + sum i_k ss_k] over the box d[4] (element offsets / strides
@@ -1349,6 +1473,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("sdp_coalesce", &sdp_coalesce);
   m.def("sdp_apply", &sdp_apply);
   m.def("emb_adagrad_apply", &emb_adagrad_apply);
+  m.def("emb_rowwise_adagrad_apply", &emb_rowwise_adagrad_apply);
+  m.def("sdp_rowwise_merge", &sdp_rowwise_merge);
   m.def("dot_fwd", &dot_fwd);
   m.def("dot_bwd", &dot_bwd, py::arg("zs"), py::arg("ldz"), py::arg("dout"), py::arg("ldo"), py::arg("dzs"),
         py::arg("lddz"), py::arg("acc_mask"), py::arg("D"), py::arg("self"), py::arg("act0") = 10);

@@ -861,6 +861,19 @@ flexmi_optimizer_t flexmi_adagrad_optimizer_create(flexmi_model_t m, double lr, 
   return wrap<flexmi_optimizer_s>(o);
 }
 
+// row-wise Adagrad (one accumulator per embedding-table row; dense parameters as Adagrad); installed
+// with flexmi_model_set_adagrad_optimizer
+flexmi_optimizer_t flexmi_rowwise_adagrad_optimizer_create(flexmi_model_t m, double lr, double eps, double wd,
+                                                           double h0) {
+  Gil g;
+  PyObject* cls = attr("flexmi.core", "RowwiseAdagradOptimizer");
+  if (!cls) return nullptr;
+  PyObject* o = PyObject_Call(cls, Py_BuildValue("(Odddd)", m->o, lr, eps, wd, h0), nullptr);
+  Py_DECREF(cls);
+  if (!o) capture_error("RowwiseAdagradOptimizer");
+  return wrap<flexmi_optimizer_s>(o);
+}
+
 int flexmi_optimizer_set_lr(flexmi_optimizer_t o, double lr) {
   Gil g;
   return call_status(o->o, "set_learning_rate", Py_BuildValue("(d)", lr));

@@ -151,6 +151,10 @@ flexmi_optimizer_t flexmi_adam_optimizer_create(flexmi_model_t m, double alpha, 
 /* element-wise Adagrad (flexmi extension; torch.optim.Adagrad with lr_decay = 0) */
 flexmi_optimizer_t flexmi_adagrad_optimizer_create(flexmi_model_t m, double lr, double epsilon, double weight_decay,
                                                    double initial_accumulator_value);
+/* row-wise Adagrad: one accumulator per embedding-table row, dense parameters as Adagrad; install it with
+   flexmi_model_set_adagrad_optimizer, release it with flexmi_optimizer_destroy */
+flexmi_optimizer_t flexmi_rowwise_adagrad_optimizer_create(flexmi_model_t m, double lr, double epsilon,
+                                                           double weight_decay, double initial_accumulator_value);
 int flexmi_optimizer_set_lr(flexmi_optimizer_t o, double lr);
 void flexmi_optimizer_destroy(flexmi_optimizer_t o);
 flexmi_initializer_t flexmi_glorot_uniform_initializer_create(int seed);

@@ -21,7 +21,8 @@
 //     banks, no atomics), the block sums its waves' copies and flushes one atomic per (row, col).
 // Backward under Adagrad (tables that are not replicated): the sparse-DP coalesce (claim / assign /
 // dups) sums the duplicate lookups of a row, then fm_emb_adagrad_apply updates the accumulator and
-// the weights of the touched rows only -- see "fused sparse Adagrad" below.
+// the weights of the touched rows only -- see "fused sparse Adagrad" below; row-wise Adagrad keeps
+// one accumulator per row and also takes replicated tables -- "fused sparse row-wise Adagrad".
 #include "common.h"
 
 #include <algorithm>
@@ -668,7 +669,7 @@ __global__ void fm_sdp_reset_counts(SdpApplySet s) {
 // 16-B accesses (D = 128: 32 lanes, two rows per wave) and two rows in flight per lane -- the
 // second one's address is clamped to the last payload row and only its stores are predicated, so
 // the loads of an iteration stay unconditional.  Other D: one wave per row, lane = column.
-// (Row-wise Adagrad -- one accumulator per row -- is a different optimizer and not provided.)
+// (Row-wise Adagrad -- one accumulator per row -- is a different optimizer: see below.)
 struct AdaDesc {
   float* W;           // [rows][D] table shard
   float* H;           // [rows][D] accumulator, same shape
@@ -748,6 +749,192 @@ __global__ void __launch_bounds__(256) fm_emb_adagrad_apply_multi(AdaSet s, cons
 // zero the counts once the apply has read them (a separate tiny launch, as fm_sdp_reset_counts)
 __global__ void fm_emb_adagrad_reset(AdaSet s) {
   if (threadIdx.x < s.n) *s.t[threadIdx.x].count = 0;
+}
+
+// ---- fused sparse row-wise Adagrad ---------------------------------------------------------------
+// One fp32 accumulator per table row ("exact row-wise Adagrad"), applied to a coalesced payload:
+//   h[r] += (1/D) sum_c g[u][c]^2;  W[r][c] -= lr g[u][c] / (sqrt(h[r]) + eps)     (r = ids[u], u < count)
+// Per touched row the kernel reads g once and read-modify-writes W: 3 D words against the 5 D of
+// the element-wise form.  D % 4 == 0: D/4 lanes own a row with 16-B accesses; the lane group is
+// the next power of two (at most 64, surplus lanes idle: D = 48 -> 12 of 16 lanes), so a row's sum
+// of squares is an xor butterfly inside the wave -- no LDS, no atomics, and every lane of the
+// group ends with the same bits.  The row's g stays in registers between the sum and the W update;
+// above D = 256 a lane takes several 16-B chunks, sums them first and re-reads g for the update.
+// Other D: one wave per row, lane = column.  The outer loop runs the same number of times in every
+// lane of the block (the shuffles need whole waves): a group past the payload's end works on the
+// clamped last row with its stores predicated off.  One row is in flight per lane group: a second,
+// clamped row as in the element-wise kernel measured slower (39.9 vs 36.0 us,
+// profiles/emb_rowwise_adagrad_ab.txt).  One lane writes h[r] and frees slot[r].  The summation order depends on D alone, so replicas that
+// apply the same payload values stay bit-identical.
+struct RwDesc {
+  float* W;           // [rows][D] table shard
+  float* h;           // [rows] accumulator, one per row
+  const int* ids;     // [nmax] unique local rows      (payload)
+  const float* g;     // [nmax][D] summed gradients   (payload)
+  int* count;         // [1] unique rows; zeroed by fm_emb_rowwise_reset after the apply
+  int* slot;          // [rows] claim slots, freed (-1) here
+  int D, nmax, vec;
+};
+struct RwSet {
+  RwDesc t[MAXT];
+  int n;
+};
+
+__device__ inline float sumsq4(const f32x4_t v) { return v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
+
+__global__ void __launch_bounds__(256) fm_emb_rowwise_apply_multi(RwSet s, const float* __restrict__ lr_p, float eps) {
+  const RwDesc& d = s.t[blockIdx.y];
+  const long cnt = min(*d.count, d.nmax);
+  if (cnt <= 0) return;                                // uniform across the block
+  const float lr = lr_p[0];
+  const float invD = 1.0f / (float)d.D;
+  if (d.vec) {
+    const int D4 = d.D >> 2;
+    const int act = D4 < 64 ? D4 : 64;                 // lanes of a group that hold columns
+    int G = 1;
+    while (G < act) G <<= 1;                           // the group: a power of two, 1..64
+    const int rpi = 256 / G;
+    const int sub = threadIdx.x / G, lc = threadIdx.x & (G - 1);
+    const bool col = lc < act;
+    const int c0 = (col ? lc : 0) * 4;                 // idle lanes load column 0 and drop it
+    for (long base = (long)blockIdx.x * rpi; base < cnt; base += (long)gridDim.x * rpi) {
+      const bool live = base + sub < cnt;              // uniform across the row's lanes
+      const long u = live ? base + sub : cnt - 1;
+      const long r = d.ids[u];
+      const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(d.g + u * d.D + c0);
+      const f32x4_t w = *reinterpret_cast<const f32x4_t*>(d.W + r * d.D + c0);
+      const float hv = d.h[r];
+      float ss = col ? sumsq4(gv) : 0.0f;
+      for (int c4 = lc + 64; c4 < D4; c4 += 64)        // D > 256: further chunks of this lane
+        ss += sumsq4(*reinterpret_cast<const f32x4_t*>(d.g + u * d.D + c4 * 4));
+      for (int off = G >> 1; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+      const float hn = hv + ss * invD;
+      const float mul = lr / (sqrtf(hn) + eps);
+      if (live && col) {
+        *reinterpret_cast<f32x4_t*>(d.W + r * d.D + c0) = w - mul * gv;
+        for (int c4 = lc + 64; c4 < D4; c4 += 64) {
+          f32x4_t* wp = reinterpret_cast<f32x4_t*>(d.W + r * d.D + c4 * 4);
+          *wp = *wp - mul * *reinterpret_cast<const f32x4_t*>(d.g + u * d.D + c4 * 4);
+        }
+      }
+      if (live && lc == 0) {
+        d.h[r] = hn;
+        d.slot[r] = -1;                                // release the claim for the next step
+      }
+    }
+  } else {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (long u = blockIdx.x * 4L + wave; u < cnt; u += (long)gridDim.x * 4) {   // uniform across the wave
+      const long r = d.ids[u];
+      float* w = d.W + r * d.D;
+      const float* gu = d.g + u * d.D;
+      float ss = 0.0f;
+      for (int c = lane; c < d.D; c += 64) ss += gu[c] * gu[c];
+      for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+      const float hn = d.h[r] + ss * invD;
+      const float mul = lr / (sqrtf(hn) + eps);
+      for (int c = lane; c < d.D; c += 64) w[c] -= mul * gu[c];
+      if (lane == 0) {
+        d.h[r] = hn;
+        d.slot[r] = -1;
+      }
+    }
+  }
+}
+
+// zero the counts once the apply has read them (a separate tiny launch, as fm_emb_adagrad_reset)
+__global__ void fm_emb_rowwise_reset(RwSet s) {
+  if (threadIdx.x < s.n) *s.t[threadIdx.x].count = 0;
+}
+
+// ---- replicated tables under row-wise Adagrad: deterministic merge of the gathered segments ------
+// Applying the R segments one after another (fm_sdp_apply) would square each replica's gradient
+// on its own; Adagrad needs the replicas' gradients of a row summed first.  Per step, after the
+// pack and the all-gather:
+//   release : free the own claim slots (they hold lookup indices after the coalesce) and zero the
+//             own count;
+//   merge   : one launch per segment in replica-rank order.  A row not seen yet takes a merged
+//             index m (one integer atomic on the merged count), records slot[r] = m, mids[m] = r
+//             and STORES its gradient; a row seen in an earlier segment ADDS into mg[slot[r]] with
+//             a plain read-modify-write (rows are unique within a segment and the launches are
+//             ordered on the stream -- no float atomics).  Every row's sum is formed in rank order
+//             on every replica: m may differ between replicas, the values may not;
+//   apply   : fm_emb_rowwise_adagrad_apply on (mids, mg, mcount); it frees the slots and zeroes the
+//             merged count.
+struct RwMerge {
+  const int* ids;     // [nmax] this segment's unique local rows
+  const float* g;     // [nmax][D] their gradients
+  const int* count;   // [1]
+  int* slot;          // [rows] -1 = not seen this step, else the merged index
+  int* mids;          // [mcap] merged rows
+  float* mg;          // [mcap][D] merged gradients
+  int* mcount;        // [1] merged rows so far
+  int rows, D, nmax, mcap, vec;
+};
+struct RwMergeSet {
+  RwMerge t[MAXT];
+  int n;
+};
+struct RwRelease {
+  const int* ids;     // own payload
+  int* count;         // own count, zeroed by fm_sdp_rowwise_reset_own
+  int* slot;
+  int rows, nmax;
+};
+struct RwReleaseSet {
+  RwRelease t[MAXT];
+  int n;
+};
+
+__global__ void __launch_bounds__(256) fm_sdp_rowwise_release(RwReleaseSet s) {
+  const RwRelease& d = s.t[blockIdx.y];
+  const long cnt = min(*d.count, d.nmax);
+  for (long u = blockIdx.x * 256L + threadIdx.x; u < cnt; u += (long)gridDim.x * 256) {
+    const int r = d.ids[u];
+    if ((unsigned)r < (unsigned)d.rows) d.slot[r] = -1;
+  }
+}
+
+__global__ void fm_sdp_rowwise_reset_own(RwReleaseSet s) {
+  if (threadIdx.x < s.n) *s.t[threadIdx.x].count = 0;
+}
+
+// one wave per segment row (lane = 16-B chunk, or column in the scalar form)
+__global__ void __launch_bounds__(256) fm_sdp_rowwise_merge(RwMergeSet s) {
+  const RwMerge& d = s.t[blockIdx.y];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long cnt = min(*d.count, d.nmax);
+  for (long u = blockIdx.x * 4L + wave; u < cnt; u += (long)gridDim.x * 4) {     // uniform across the wave
+    const int r = d.ids[u];
+    if ((unsigned)r >= (unsigned)d.rows) continue;
+    int m = 0;
+    if (lane == 0) {
+      m = d.slot[r];
+      if (m < 0) {
+        m = atomicAdd(d.mcount, 1);
+        if (m < d.mcap) {
+          d.slot[r] = m;
+          d.mids[m] = r;
+        }
+        m = ~m;                                        // negative: a first sight, the row is stored
+      }
+    }
+    m = __shfl(m, 0, 64);
+    const bool first = m < 0;
+    if (first) m = ~m;
+    if (m >= d.mcap) continue;                         // cannot happen: mcap = min(rows, R * nmax)
+    const float* gu = d.g + u * d.D;
+    float* mo = d.mg + (long)m * d.D;
+    if (d.vec) {
+      for (int c4 = lane; c4 < (d.D >> 2); c4 += 64) {
+        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(gu + c4 * 4);
+        f32x4_t* mp = reinterpret_cast<f32x4_t*>(mo + c4 * 4);
+        *mp = first ? v : *mp + v;
+      }
+    } else {
+      for (int c = lane; c < d.D; c += 64) mo[c] = first ? gu[c] : mo[c] + gu[c];
+    }
+  }
 }
 
 }  // namespace
@@ -974,5 +1161,68 @@ extern "C" void fm_emb_adagrad_apply(int n, float* const* W, float* const* H, co
     dim3 grid((unsigned)std::max(1, std::min((nm + 7) / 8, 2048)), m);
     hipLaunchKernelGGL(fm_emb_adagrad_apply_multi, grid, dim3(256), 0, st, s, lr, eps);
     hipLaunchKernelGGL(fm_emb_adagrad_reset, dim3(1), dim3(64), 0, st, s);
+  }
+}
+
+// ---- row-wise Adagrad launchers --------------------------------------------------------------
+// one payload (ids, g, count) per table -> h / W row updates, slots freed, counts zeroed;
+// h[k] holds one fp32 per table row; nmax[k] = capacity of table k's payload
+extern "C" void fm_emb_rowwise_adagrad_apply(int n, float* const* W, float* const* h, const int* D,
+                                             const int* const* ids, const float* const* g, int* const* count,
+                                             int* const* slot, const int* nmax, const float* lr, float eps,
+                                             hipStream_t st) {
+  if (n <= 0) return;
+  for (size_t base = 0; base < (size_t)n; base += MAXT) {
+    const int m = (int)std::min<size_t>(MAXT, n - base);
+    RwSet s;
+    int nm = 1;
+    for (int i = 0; i < m; ++i) {
+      const int k = (int)base + i;
+      const bool vec = D[k] % 4 == 0 && ((((uintptr_t)W[k]) | ((uintptr_t)g[k])) & 15) == 0;
+      s.t[i] = RwDesc{W[k], h[k], ids[k], g[k], count[k], slot[k], D[k], nmax[k], vec ? 1 : 0};
+      nm = std::max(nm, nmax[k]);
+    }
+    s.n = m;
+    // >= 4 rows per block-iteration in either form
+    dim3 grid((unsigned)std::max(1, std::min((nm + 7) / 8, 2048)), m);
+    hipLaunchKernelGGL(fm_emb_rowwise_apply_multi, grid, dim3(256), 0, st, s, lr, eps);
+    hipLaunchKernelGGL(fm_emb_rowwise_reset, dim3(1), dim3(64), 0, st, s);
+  }
+}
+
+// release the own claims, then merge the segs gathered segments (seg_*[sg * n + k]) of n replicated
+// tables in segment order into (mids, mg, mcount); mcount must be 0 on entry (the apply zeroes it)
+extern "C" void fm_sdp_rowwise_merge_segments(int n, int segs, const int* rows, const int* D, const int* const* seg_ids,
+                                              const float* const* seg_g, const int* const* seg_count,
+                                              const int* const* own_ids, int* const* own_count, int* const* slot,
+                                              int* const* mids, float* const* mg, int* const* mcount, const int* nmax,
+                                              const int* mcap, hipStream_t st) {
+  if (n <= 0) return;
+  for (size_t base = 0; base < (size_t)n; base += MAXT) {
+    const int m = (int)std::min<size_t>(MAXT, n - base);
+    int nm = 1;
+    RwReleaseSet rs;
+    for (int i = 0; i < m; ++i) {
+      const int k = (int)base + i;
+      rs.t[i] = RwRelease{own_ids[k], own_count[k], slot[k], rows[k], nmax[k]};
+      nm = std::max(nm, nmax[k]);
+    }
+    rs.n = m;
+    hipLaunchKernelGGL(fm_sdp_rowwise_release, dim3((unsigned)std::max(1, std::min((nm + 255) / 256, 1024)), m), dim3(256),
+                       0, st, rs);
+    hipLaunchKernelGGL(fm_sdp_rowwise_reset_own, dim3(1), dim3(64), 0, st, rs);
+    dim3 grid((unsigned)std::max(1, std::min((nm + 3) / 4, 2048)), m);
+    for (int sg = 0; sg < segs; ++sg) {
+      RwMergeSet s;
+      for (int i = 0; i < m; ++i) {
+        const int k = (int)base + i;
+        const float* gs = seg_g[sg * n + k];
+        const bool vec = D[k] % 4 == 0 && ((((uintptr_t)gs) | ((uintptr_t)mg[k])) & 15) == 0;
+        s.t[i] = RwMerge{seg_ids[sg * n + k], gs, seg_count[sg * n + k], slot[k], mids[k], mg[k], mcount[k],
+                         rows[k], D[k], nmax[k], mcap[k], vec ? 1 : 0};
+      }
+      s.n = m;
+      hipLaunchKernelGGL(fm_sdp_rowwise_merge, grid, dim3(256), 0, st, s);
+    }
   }
 }

@@ -42,7 +42,8 @@ def dlrm_hetero_strategy(num_emb):
 
 
 def _model(name, gpus, batch, small, optimizer="sgd"):
-    from flexmi.core import AdagradOptimizer, AdamOptimizer, FFConfig, FFModel, SGDOptimizer
+    from flexmi.core import (AdagradOptimizer, AdamOptimizer, FFConfig, FFModel, RowwiseAdagradOptimizer,
+                             SGDOptimizer)
     from flexmi.models import zoo
     cfg = FFConfig()
     cfg.device = "cpu"
@@ -51,8 +52,10 @@ def _model(name, gpus, batch, small, optimizer="sgd"):
     m = FFModel(cfg)
     built = zoo.build(name, m, small=small)
     # the optimizer decides how tables are priced: SGD and Adagrad update non-replicated tables
-    # sparsely, and only SGD trains replicated ones by sparse data parallelism
-    m.optimizer = {"sgd": SGDOptimizer, "adagrad": AdagradOptimizer, "adam": AdamOptimizer}[optimizer](m, built.lr)
+    # sparsely, SGD trains replicated ones by sparse data parallelism where that moves fewer bytes,
+    # row-wise Adagrad always (merged exchange) and never splits a table by columns
+    m.optimizer = {"sgd": SGDOptimizer, "adagrad": AdagradOptimizer, "adam": AdamOptimizer,
+                   "rowwise_adagrad": RowwiseAdagradOptimizer}[optimizer](m, built.lr)
     return m
 
 
@@ -75,7 +78,7 @@ def main(argv=None):
         p.add_argument("--gpus", type=int, default=8)
         p.add_argument("--batch", type=int, default=0, help="global batch (default 64 per GPU; DLRM 8192)")
         p.add_argument("--small", action="store_true")
-        p.add_argument("--optimizer", choices=["sgd", "adagrad", "adam"], default="sgd")
+        p.add_argument("--optimizer", choices=["sgd", "adagrad", "rowwise_adagrad", "adam"], default="sgd")
         p.add_argument("--strategy", help="strategy .pb (simulate) / initial state (search)")
         p.add_argument("--trace", help="write the predicted timeline as Chrome trace JSON")
         p.add_argument("--machine", help="machine model JSON override")

@@ -4,7 +4,7 @@ from .config import FFConfig  # noqa
 from .tensor import Tensor, Parameter  # noqa
 from .initializers import (Initializer, GlorotUniformInitializer, ZeroInitializer, UniformInitializer,  # noqa
                            NormInitializer, NormalInitializer, ConstantInitializer)
-from .optimizers import SGDOptimizer, AdamOptimizer, AdagradOptimizer, Optimizer  # noqa
+from .optimizers import SGDOptimizer, AdamOptimizer, AdagradOptimizer, RowwiseAdagradOptimizer, Optimizer  # noqa
 from .loss_metrics import PerfMetrics  # noqa
 from .dataloader import SingleDataLoader, DataLoader2D, DataLoader4D, NetConfig, PrefetchLoader  # noqa
 from .model import FFModel  # noqa

@@ -22,9 +22,26 @@ the identity.  SGD without momentum / weight decay and Adagrad without weight de
 shape and every step updates only the looked-up rows, duplicates summed BEFORE the gradient is
 squared (``csrc/kernels/embedding.hip`` fm_sdp_coalesce + fm_emb_adagrad_apply) -- equal to dense
 Adagrad.  Replicated tables under Adagrad take the dense path (``sparse_dp_capable`` is False:
-applying the replicas' segments one by one is not Adagrad of the summed gradient).  Not provided:
-row-wise Adagrad (one accumulator per row), host-placed tables under Adagrad, ``lr_decay``, and
-Adagrad in the native C++ engine.
+applying the replicas' segments one by one is not Adagrad of the summed gradient).
+
+Row-wise Adagrad (``RowwiseAdagradOptimizer``) is the form DLRM-class models are trained with:
+dense parameters as under Adagrad, every embedding table sparsely with ONE accumulator per row
+(``G[r,:]`` = the row's gradient of the step, duplicate lookups summed over the batch and the
+replicas; ``D`` = the table's embedding dim):
+
+  h[r] += (1/D)·Σ_c G[r,c]²  (h starts at ``initial_accumulator_value``); W[r,c] -= lr·G[r,c]/(sqrt(h[r])+ε)
+
+``h`` is stored ``[rows held, 1]`` (1/D of the element-wise accumulator), an untouched row keeps
+``h`` and ``W``.  Whole tables and row-range shards apply their coalesced payload with
+fm_emb_rowwise_adagrad_apply; tables replicated over R ranks all-gather the payloads as sparse
+data parallelism does, merge the R segments in replica-rank order (summed BEFORE squaring, the
+same fp32 operations on every replica) and apply the merged payload, so the replicas' ``W`` and
+``h`` stay bit-identical.  Rejected at compile: column-split tables (a row's sum of squares would
+span ranks), host-placed tables, ``weight_decay != 0`` with a table in the model, and replicated
+tables with ``FLEXMI_SPARSE_DP=0``.
+
+Not provided: host-placed tables under either Adagrad, ``lr_decay``, and Adagrad in the native
+C++ engine.
 """
 from __future__ import annotations
 
@@ -186,3 +203,24 @@ class AdagradOptimizer(Optimizer):
 
     def load_state_dict(self, d):
         self.lr = d.get("lr", self.lr)
+
+
+class RowwiseAdagradOptimizer(AdagradOptimizer):
+    """Row-wise Adagrad: dense parameters exactly as :class:`AdagradOptimizer`; every embedding
+    table sparsely with one fp32 accumulator per row, ``h[r] += mean_c(G[r,c]^2)``,
+    ``W[r,:] -= lr * G[r,:] / (sqrt(h[r]) + eps)`` (module docstring)."""
+
+    # a table has no dense path under this optimizer: it is always sparse, replicated ones by the
+    # merged touched-row exchange
+    sparse_capable = True
+    sparse_dp_capable = True
+    sparse_dp_always = True     # whatever the byte comparison of Embedding.sdp_prefer_sparse says
+
+    def table_pc_ok(self, op, pc):
+        """Strategy search hook: False for a table placement the executor rejects -- a column
+        split (a row's sum of squares would span ranks)."""
+        return op._grid(pc)[1] == 1
+
+    def table_state_bytes(self, rows, cols):
+        """Optimizer state of a table shard of ``rows x cols``: one fp32 per row."""
+        return 4.0 * rows

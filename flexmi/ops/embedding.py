@@ -14,6 +14,8 @@ other tables use 256-B-contiguous fp32 atomics; tiny tables accumulate in LDS fi
 Under Adagrad (no weight decay, table not replicated) the backward coalesces the lookups into
 (unique row, summed gradient) payloads and updates accumulator and weights of those rows only
 (``adagrad_group``); still no dense gradient, one extra table-sized buffer (the accumulator).
+Under row-wise Adagrad every table is trained that way with one accumulator per ROW
+(``rowwise_group``; replicated tables by a merged sparse-DP exchange, ``sdp_apply_rowwise``).
 SOAP: sample split, **column (parameter) split** of the table, whole-table placement
 (``dims=[1,1]``, device k) -- a 100 M-row table fits one MI355X's 288 GB of HBM -- and **row
 split** (flexmi extension of the strategy format: a third internal degree, ``dims=[c, n, r]``):
@@ -116,6 +118,27 @@ class SparseAdagradState(SparseDPState):
         pass
 
 
+class SparseRowwiseDPState(SparseDPState):
+    """Sparse-DP payload buffers of a replicated table group under row-wise Adagrad, plus the merged
+    payload the R gathered segments are summed into before the apply (see
+    :meth:`Embedding.sdp_apply`): per table at most ``min(rows, R * lookups)`` unique rows, their
+    fp32 gradient sums and one count."""
+
+    def __init__(self, ops, ctxs, holders, rank):
+        super().__init__(ops, ctxs, holders, rank)
+        dev = ctxs[0].weights[0].device
+        self.mcap = [max(1, min(c.weights[0].shape[0], self.R * c.inputs[0].numel())) for c in ctxs]
+        self.mids, self.mg, self.mcount = [], [], []
+        if ctxs[0].hip:     # the CPU backend merges with torch.unique and needs no buffers
+            self.mids = [torch.zeros(m, dtype=torch.int32, device=dev) for m in self.mcap]
+            self.mg = [torch.zeros(m * c.weights[0].shape[1], dtype=torch.float32, device=dev)
+                       for m, c in zip(self.mcap, ctxs)]
+            self.mcount = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in ctxs]
+
+    def merged_bytes(self):
+        return sum(t.numel() * 4 for t in self.mids + self.mg + self.mcount)
+
+
 class Embedding(Op):
     op_type = OperatorType.OP_EMBEDDING
     name_prefix = "Embed"
@@ -140,6 +163,9 @@ class Embedding(Op):
         # sparse_adagrad = epsilon when the table is trained by the fused sparse Adagrad update
         # (non-replicated tables; accumulator in ctx.weight_state[0]["h"]), else None
         self.sparse_adagrad = None
+        # sparse_rowwise = epsilon when the table is trained by row-wise Adagrad (one accumulator per
+        # row, ctx.weight_state[0]["h"] shaped [rows, 1]; replicated tables also carry sparse_dp)
+        self.sparse_rowwise = None
 
     def splittable_dims(self):
         return {0, 1}
@@ -238,6 +264,9 @@ class Embedding(Op):
         if self.sparse_adagrad is not None:
             Embedding.adagrad_group([self], [ctx])
             return
+        if self.sparse_rowwise is not None:
+            Embedding.rowwise_group([self], [ctx])
+            return
         if self.sparse_sgd:
             # fused sparse SGD (no dense grad): W[idx] -= lr * dy  (duplicates summed first)
             scale = 1.0 / idx.shape[1] if self.aggr == AggrMode.AGGR_MODE_AVG else 1.0
@@ -277,6 +306,7 @@ class Embedding(Op):
         """Executor fusion: independent embeddings with the same placement run as ONE launch."""
         return (ca.outputs[0].dtype == cb.outputs[0].dtype and a.sparse_sgd == b.sparse_sgd
                 and getattr(a, "sparse_adagrad", None) == getattr(b, "sparse_adagrad", None)
+                and getattr(a, "sparse_rowwise", None) == getattr(b, "sparse_rowwise", None)
                 and getattr(a, "sparse_dp", None) == getattr(b, "sparse_dp", None)
                 and ca.inputs[0].shape[0] == cb.inputs[0].shape[0])
 
@@ -300,6 +330,9 @@ class Embedding(Op):
             return
         if ops[0].sparse_adagrad is not None:
             Embedding.adagrad_group(ops, ctxs)
+            return
+        if ops[0].sparse_rowwise is not None:
+            Embedding.rowwise_group(ops, ctxs)
             return
         scales = [1.0 / c.inputs[0].shape[1] if op.aggr == AggrMode.AGGR_MODE_AVG else 1.0 for op, c in zip(ops, ctxs)]
         if ops[0].sparse_sgd:
@@ -335,7 +368,9 @@ class Embedding(Op):
         c0 = ctxs[0]
         st = c0.saved.get("sdp")
         if st is None:
-            st = SparseDPState(ops, ctxs, holders, rank)
+            # row-wise Adagrad sums the gathered segments before it squares them: merged buffers
+            cls = SparseRowwiseDPState if ops[0].sparse_rowwise is not None else SparseDPState
+            st = cls(ops, ctxs, holders, rank)
             c0.saved["sdp"] = st
         return st
 
@@ -366,6 +401,9 @@ class Embedding(Op):
     def sdp_apply(ops, ctxs):
         st = ctxs[0].saved["sdp"]
         lr = ctxs[0].lr
+        if ops[0].sparse_rowwise is not None:
+            Embedding.sdp_apply_rowwise(ops, ctxs, st)
+            return
         if ctxs[0].hip:
             K.C().sdp_apply([c.weights[0] for c in ctxs], [t for s in range(st.R) for t in st.rids[s]],
                             [t for s in range(st.R) for t in st.rg[s]], [t for s in range(st.R) for t in st.rcount[s]],
@@ -385,7 +423,7 @@ class Embedding(Op):
     # into (unique local rows, summed gradients) -- duplicates are summed BEFORE the gradient is
     # squared -- then update H and W of those rows only.  Untouched rows have gradient 0 and keep H
     # and W, so this equals dense element-wise Adagrad without a table-sized gradient buffer.
-    # Replicated tables are not handled here (they stay dense); row-wise Adagrad is not provided.
+    # Replicated tables are not handled here (they stay dense); row-wise Adagrad: rowwise_group below.
     @staticmethod
     def adagrad_group(ops, ctxs):
         c0 = ctxs[0]
@@ -416,6 +454,77 @@ class Embedding(Op):
                 hr = h[rows] + g * g
                 h[rows] = hr
                 w[rows] = w[rows] - lrf * g / (hr.sqrt() + float(op.sparse_adagrad))
+
+    # ---------------------------------------------------------- fused sparse row-wise Adagrad
+    # RowwiseAdagradOptimizer: one accumulator per row, h[r] += mean_c(G[r,c]^2),
+    # W[r,:] -= lr G[r,:] / (sqrt(h[r]) + eps), G = the row's gradient with every duplicate lookup
+    # summed first.  Whole tables and row shards: coalesce, then apply the payload where it was
+    # packed (rowwise_group).  Replicated tables run pack / all-gather as sparse DP does and then
+    # sdp_apply_rowwise: the R segments are summed per row in replica-rank order into a merged
+    # payload -- BEFORE the square, and by the same fp32 additions on every replica -- which the
+    # same apply kernel consumes, so the replicas' W and h stay bit-identical.
+    @staticmethod
+    def _rowwise_eps(ops):
+        eps = {float(op.sparse_rowwise) for op in ops}
+        assert len(eps) == 1
+        return eps.pop()
+
+    @staticmethod
+    def _rowwise_rule(w, h, rows, g, lrf, eps):
+        """The rule on unique local ``rows`` with their summed gradients ``g`` [n, D] (torch)."""
+        hr = h[rows, 0] + (g * g).sum(1) / w.shape[1]
+        h[rows, 0] = hr
+        w[rows] = w[rows] - lrf * g / (hr.sqrt() + eps).unsqueeze(1)
+
+    @staticmethod
+    def rowwise_group(ops, ctxs):
+        c0 = ctxs[0]
+        st = c0.saved.get("rowwise")
+        if st is None:
+            st = c0.saved["rowwise"] = SparseAdagradState(ops, ctxs, c0.rank)
+        Embedding.sdp_pack(ops, ctxs, st)
+        lr = c0.lr
+        H = [c.weight_state[0]["h"] for c in ctxs]
+        if c0.hip:
+            K.C().emb_rowwise_adagrad_apply([c.weights[0] for c in ctxs], H, st.ids[0], st.g[0], st.count[0], st.slot,
+                                            lr, Embedding._rowwise_eps(ops))
+            return
+        lrf = lr.to(torch.float32)
+        for k, (op, c) in enumerate(zip(ops, ctxs)):
+            n = int(st.count[0][k].item())
+            if n:
+                D = c.weights[0].shape[1]
+                Embedding._rowwise_rule(c.weights[0], H[k], st.ids[0][k][:n].long(), st.g[0][k][:n * D].view(n, D),
+                                        lrf, float(op.sparse_rowwise))
+
+    @staticmethod
+    def sdp_apply_rowwise(ops, ctxs, st):
+        lr = ctxs[0].lr
+        H = [c.weight_state[0]["h"] for c in ctxs]
+        if ctxs[0].hip:
+            # release the own claims, merge the segments in rank order, apply the merged payload
+            K.C().sdp_rowwise_merge([t for s in range(st.R) for t in st.rids[s]],
+                                    [t for s in range(st.R) for t in st.rg[s]],
+                                    [t for s in range(st.R) for t in st.rcount[s]],
+                                    st.ids[st.seg], st.count[st.seg], st.slot, st.mids, st.mg, st.mcount,
+                                    [c.weights[0].shape[1] for c in ctxs], st.R)
+            K.C().emb_rowwise_adagrad_apply([c.weights[0] for c in ctxs], H, st.mids, st.mg, st.mcount, st.slot, lr,
+                                            Embedding._rowwise_eps(ops))
+            return
+        lrf = lr.to(torch.float32)
+        for k, (op, c) in enumerate(zip(ops, ctxs)):
+            w = c.weights[0]
+            D = w.shape[1]
+            ns = [int(st.rcount[s][k].item()) for s in range(st.R)]
+            if not sum(ns):
+                continue
+            uniq, inv = torch.unique(torch.cat([st.rids[s][k][:ns[s]].long() for s in range(st.R)]), return_inverse=True)
+            summed = torch.zeros((uniq.numel(), D), dtype=torch.float32)
+            o = 0
+            for s in range(st.R):       # rank order; rows are unique within a segment
+                summed.index_add_(0, inv[o:o + ns[s]], st.rg[s][k][:ns[s] * D].view(ns[s], D))
+                o += ns[s]
+            Embedding._rowwise_rule(w, H[k], uniq, summed, lrf, float(op.sparse_rowwise))
 
     CLAIM = True                 # owner-computes path for mostly-unique tables (tests may switch it)
     # owner-computes when rows exceed CLAIM_RATIO x lookups per step (few enough duplicates for the

@@ -144,6 +144,12 @@ class SimGraph:
         # applying the replica segments one by one is not Adagrad of the summed gradient, so a
         # replicated table under Adagrad is priced dense, as the executor trains it
         self.sparse_dp_ok = self.sparse_ok and bool(getattr(opt, "sparse_dp_capable", False))
+        # optimizer hooks (row-wise Adagrad): table placements the executor would reject, replicated
+        # tables trained by sparse DP whatever the byte comparison says (no dense alternative), and
+        # the optimizer state of a sparsely trained table shard (one fp32 per row, not per element)
+        self.table_pc_ok = getattr(opt, "table_pc_ok", None)
+        self.sdp_always = self.sparse_dp_ok and bool(getattr(opt, "sparse_dp_always", False))
+        self.table_state_bytes = getattr(opt, "table_state_bytes", None)
         self.ops = list(model.layers)
         md = self.machine.native_dict()
         if not md["xchg_chunks"]:
@@ -167,6 +173,10 @@ class SimGraph:
                 pc = extra[op.name]
                 if op.valid_pc(pc) and max(pc.device_ids) < ndev and pc not in cl:
                     cl.append(pc)
+            if self.table_pc_ok is not None and op.op_type == OperatorType.OP_EMBEDDING:
+                keep = [pc for pc in cl if self.table_pc_ok(op, pc)]
+                if keep:            # dropped only while a candidate remains
+                    cl = keep
             self.cands.append(cl)
             self.sim.add_op(op.name, [tid[t.guid] for t in op.inputs], [tid[o.guid] for o in op.outputs],
                             [self._cand(op, pc) for pc in cl], ndev, _rowwise(op))
@@ -211,9 +221,11 @@ class SimGraph:
                     box = lay.part_box(p)
                     rows = max(1, box[0][1] - box[0][0])
                     lookups = -(-B // R) * bag
-                    sparse = Embedding.sdp_prefer_sparse(rows, vol // rows, lookups, R)
+                    sparse = self.sdp_always or Embedding.sdp_prefer_sparse(rows, vol // rows, lookups, R)
                     if sparse:
                         sdp_words = float(R * op.sdp_payload_words(lookups, vol // rows))
+                        if self.sdp_always:     # + the merged payload the R segments are summed into
+                            sdp_words += float(min(rows, R * lookups) * (vol // rows + 1))
                 if len(h) > 1:
                     if sparse:
                         # replicated table with the sparse optimizer = the executor's sparse data
@@ -236,8 +248,15 @@ class SimGraph:
                 for d in h:
                     if sparse:
                         # the table + (sparse DP) the R-slot receive buffer of the all-gather +
-                        # one table-sized buffer per optimizer state (sparse Adagrad: h)
-                        mem[d] = mem.get(d, 0.0) + vol * 4.0 * (1 + self.nstates) + sdp_words * 4.0
+                        # one table-sized buffer per optimizer state (sparse Adagrad: h; row-wise
+                        # Adagrad: one fp32 per row)
+                        if self.table_state_bytes is not None:
+                            box = lay.part_box(p)
+                            rows = max(1, box[0][1] - box[0][0])
+                            state_b = float(self.table_state_bytes(rows, vol // rows))
+                        else:
+                            state_b = vol * 4.0 * self.nstates
+                        mem[d] = mem.get(d, 0.0) + vol * 4.0 + state_b + sdp_words * 4.0
                     else:
                         mem[d] = mem.get(d, 0.0) + vol * (4.0 + 4.0 + 2.0 + 4.0 * self.nstates)
                         upd_bytes[d] = upd_bytes.get(d, 0.0) + vol * 4.0

@@ -10,7 +10,7 @@ compiles (graph, strategy, rank) into:
     distribution than the producer made -- including partial-sum reductions in backward;
   * flat fp32 master/grad/optimizer-state buffers per gradient-sync group with bf16 compute
     mirrors, bucketed for async RCCL all-reduce overlapped with backward;
-  * a fused sparse-SGD / sparse-Adagrad path for non-replicated embedding tables (no dense gradient).
+  * a fused sparse-SGD / sparse-Adagrad / row-wise Adagrad path for embedding tables (no dense gradient).
 
 All buffers are allocated once, so the whole step can be captured in a hipGraph
 (``Executor.capture_step``) -- the analogue of Legion tracing (``dlrm.cc:178-185``).
@@ -28,7 +28,7 @@ import torch
 
 from flexmi.core.loss_metrics import NUM_SLOTS, PerfMetrics, loss_and_metrics_torch
 from flexmi.core.initializers import _native_cpu
-from flexmi.core.optimizers import AdagradOptimizer, AdamOptimizer, SGDOptimizer
+from flexmi.core.optimizers import AdagradOptimizer, AdamOptimizer, RowwiseAdagradOptimizer, SGDOptimizer
 from flexmi.core.types import DataType, LossType, to_torch_dtype
 from flexmi.ops.base import OpCtx
 from flexmi.parallel.layout import Layout, ParallelConfig, ReshardPlan, box_intersect, box_volume
@@ -1126,6 +1126,20 @@ class Executor:
         bag = op.inputs[0].dims[1] if len(op.inputs[0].dims) > 1 else 1
         return Embedding.sdp_prefer_sparse(rows, cols, -(-B // R) * bag, R)
 
+    def _check_rowwise_table(self, op, pc, lay):
+        """Row-wise Adagrad trains every table sparsely; reject what that path cannot do."""
+        why = None
+        if pc.device_type == ParallelConfig.CPU:
+            why = "host-placed tables (device_type=CPU) are not supported"
+        elif op._grid(pc)[1] > 1:
+            why = "column-split tables are not supported (a row's sum of squares would span ranks)"
+        elif self.optimizer.weight_decay != 0.0:
+            why = "weight_decay != 0 is not supported with embedding tables (a table has no dense path)"
+        elif lay.replication() > 1 and not SPARSE_DP:
+            why = "replicated tables need sparse data parallelism (FLEXMI_SPARSE_DP=0 is set)"
+        if why:
+            raise NotImplementedError(f"{op.name}: row-wise Adagrad: {why}")
+
     def _build_weights(self, ops):
         self.wentries: Dict[int, WeightEntry] = {}
         groups: "OrderedDict[tuple, SyncGroup]" = OrderedDict()
@@ -1135,6 +1149,11 @@ class Executor:
         # dense groups (the replica all-reduce sums the gradients before they are squared -- sparse
         # DP would not), and host-placed tables are not supported
         adagrad_ok = isinstance(self.optimizer, AdagradOptimizer) and self.optimizer.sparse_capable
+        # row-wise Adagrad (checked first: it is a subclass): every table is trained sparsely with
+        # one accumulator per row held (Embedding.rowwise_group), replicated ones by the merged
+        # touched-row exchange (Embedding.sdp_apply_rowwise); a table has no dense path, so what
+        # the sparse path cannot do is rejected here
+        rowwise = isinstance(self.optimizer, RowwiseAdagradOptimizer)
         for op in reversed(ops):  # backward order => buckets fill contiguously
             pc = self.pcs[op.guid]
             lays = op.weight_layouts(pc)
@@ -1144,9 +1163,11 @@ class Executor:
                     continue
                 e = WeightEntry(w, op, wi, lays[wi], self.rank)
                 self.wentries[w.guid] = e
+                from flexmi.core.types import OperatorType
+                if rowwise and op.op_type == OperatorType.OP_EMBEDDING:
+                    self._check_rowwise_table(op, pc, lays[wi])     # on every rank, holder or not
                 if e.box is None:
                     continue
-                from flexmi.core.types import OperatorType
                 if pc.device_type == ParallelConfig.CPU:
                     # heterogeneous placement (dlrm_strategy_hetero.cc): the table
                     # lives in (pinned) host memory and its lookups / sparse SGD run on the host
@@ -1162,6 +1183,19 @@ class Executor:
                 if op.op_type == OperatorType.OP_EMBEDDING:
                     op.sparse_dp = None
                     op.sparse_adagrad = None
+                    op.sparse_rowwise = None
+                    if rowwise:
+                        e.sparse = True
+                        op.sparse_sgd = False
+                        op.sparse_rowwise = self.optimizer.epsilon
+                        if lays[wi].replication() > 1:
+                            # no dense alternative, so _sdp_pays is not consulted
+                            op.sparse_dp = tuple(sorted(e.holders))
+                        e.master = self._alloc(e.shape, torch.float32)
+                        e.compute = e.master
+                        e.state = {"h": torch.full((e.shape[0], 1), self.optimizer.state_init("h"), dtype=torch.float32,
+                                                   device=self.device)}
+                        continue
                     if adagrad_ok and lays[wi].replication() == 1:
                         e.sparse = True
                         op.sparse_sgd = False
@@ -2511,7 +2545,9 @@ class Executor:
             st = c.saved.get("sdp")
             if st is not None:
                 sdp += (st.send.numel() + st.recv.numel()) * 4 + sum(t.numel() * 4 for t in st.slot + st.cid)
-        # optimizer state held per sparse table (Adagrad: h, the table's shape)
+                if hasattr(st, "merged_bytes"):      # row-wise Adagrad: the merged payload
+                    sdp += st.merged_bytes()
+        # optimizer state held per sparse table (Adagrad: h, the table's shape; row-wise: [rows, 1])
         sst = sum(t.numel() * 4 for e in self.wentries.values() if e.sparse for t in e.state.values())
         return {"activations": n, "dense_params": w, "sparse_tables": sp, "sparse_dp_payload": sdp,
                 "sparse_opt_state": sst}

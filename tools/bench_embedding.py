@@ -6,7 +6,12 @@ sizes of the MLPerf DLRM set: per-table time, effective bytes/s.  hipGraph of re
 bf16 output gradients) under sparse Adagrad (fm_sdp_coalesce + fm_emb_adagrad_apply) and under the
 sparse SGD the executor runs today (embedding_bwd_multi with its claim buffers), timed alternately
 in the same process, each next to its byte model.  Uniformly drawn indices; tables above
-``--max-rows`` rows are cut to that many (their lookups stay all but unique either way)."""
+``--max-rows`` rows are cut to that many (their lookups stay all but unique either way).
+
+``--optimizer rowwise_adagrad``: the same A/B for row-wise Adagrad -- coalesce + row-wise apply
+(fm_emb_rowwise_adagrad_apply) against coalesce + element-wise apply, alternated in one process.  Both share the coalesce, so the difference of two
+timings is the difference of the applies; per-kernel times come from a kernel trace of the same
+command."""
 import argparse
 import json
 import sys
@@ -115,9 +120,61 @@ def adagrad_ab(B, max_rows, rounds, out):
             fh.write(line + "\n")
 
 
+def rowwise_ab(B, max_rows, rounds, out):
+    from flexmi.models.dlrm import MLPERF_TABLES
+    dev = torch.device("cuda")
+    D = 128
+    rows = [min(r, max_rows) for r in MLPERF_TABLES]
+    lr = torch.tensor([0.01], device=dev)
+    idx = [torch.randint(0, r, (B, 1), device=dev) for r in rows]
+    dy = [(torch.randn(B, D, device=dev) * 1e-3).bfloat16() for _ in rows]
+    ld = [d.stride(0) for d in dy]
+    one, zero = [1.0] * len(rows), [0] * len(rows)
+    U = sum(int(torch.unique(i).numel()) for i in idx)
+    n = B * len(rows)
+    # one table set and one coalesce buffer set for every form: same rows, same payloads
+    W = [torch.randn(r, D, device=dev) for r in rows]
+    H = [torch.full((r, D), 0.1, device=dev) for r in rows]
+    h = [torch.full((r, 1), 0.1, device=dev) for r in rows]
+    slot = [torch.full((r,), -1, dtype=torch.int32, device=dev) for r in rows]
+    cid = [torch.empty(B, dtype=torch.int32, device=dev) for _ in rows]
+    ids = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in rows]
+    g = [torch.zeros(B * D, dtype=torch.float32, device=dev) for _ in rows]
+    cnt = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in rows]
+
+    def coalesce():
+        K.C().sdp_coalesce(W, idx, dy, ld, one, zero, slot, cid, ids, g, cnt)
+
+    def elementwise():
+        coalesce()
+        K.C().emb_adagrad_apply(W, H, ids, g, cnt, slot, lr, 1e-10)
+
+    def rowwise():
+        coalesce()
+        K.C().emb_rowwise_adagrad_apply(W, h, ids, g, cnt, slot, lr, 1e-10)
+    # bytes the applies need, from the shapes (U unique rows): g read, W read-modify-write, ids read,
+    # slot release, and H read-modify-write (element-wise: D words; row-wise: one word)
+    by = {"elementwise": U * (D * 4 + 2 * D * 4 + 2 * D * 4 + 4 + 4),
+          "rowwise": U * (D * 4 + 2 * D * 4 + 2 * 4 + 4 + 4)}
+    forms = {"elementwise": elementwise, "rowwise": rowwise}
+    t = {k: [] for k in forms}
+    for _ in range(rounds):                      # alternate the forms: same neighbours, same clocks
+        for k, fn in forms.items():
+            t[k].append(timed(fn))
+    rec = {"B": B, "tables": len(rows), "D": D, "max_rows": max_rows, "lookups": n, "unique_rows": U,
+           "model_bytes_apply": by}
+    for k, v in t.items():
+        rec[k] = {"coalesce_plus_apply_us": round(min(v), 2), "us_all": [round(x, 2) for x in v]}
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out:
+        with open(out, "a") as fh:
+            fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--optimizer", choices=["sgd", "adagrad"], default="sgd")
+    ap.add_argument("--optimizer", choices=["sgd", "adagrad", "rowwise_adagrad"], default="sgd")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--max-rows", type=int, default=4000000)
     ap.add_argument("--rounds", type=int, default=3)
@@ -125,6 +182,8 @@ def main():
     a = ap.parse_args()
     if a.optimizer == "adagrad":
         return adagrad_ab(a.batch, a.max_rows, a.rounds, a.out)
+    if a.optimizer == "rowwise_adagrad":
+        return rowwise_ab(a.batch, a.max_rows, a.rounds, a.out)
     dev = torch.device("cuda")
     D = 128
     for B in (8192, 65536):
