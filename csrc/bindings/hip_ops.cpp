@@ -545,57 +545,91 @@ void sdp_coalesce(std::vector<torch::Tensor> W, std::vector<torch::Tensor> idx, 
                   cur());
 }
 
+void check_i32(const torch::Tensor& t, const char* who, const char* what) {
+  check_cuda(t, what);
+  TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.is_contiguous(), who, " ", what, ": contiguous int32");
+}
+
+// the gathered payloads of n tables, segment-major: seg_*[s * n + k] = table k's payload in segment s
+// (nmax[k] ids, nmax[k] x D[k] gradients, one count)
+struct SegArgs {
+  std::vector<const int*> ids, count;
+  std::vector<const float*> g;
+  std::vector<int> nmax;
+};
+
+SegArgs seg_args(const char* who, const std::vector<torch::Tensor>& seg_ids, const std::vector<torch::Tensor>& seg_g,
+                 const std::vector<torch::Tensor>& seg_count, size_t n, int64_t segs, const std::vector<int>& D) {
+  TORCH_CHECK(segs >= 1 && seg_ids.size() == n * segs && seg_g.size() == n * segs && seg_count.size() == n * segs, who,
+              ": segs x tables payload views");
+  SegArgs a;
+  for (size_t j = 0; j < n * segs; ++j) {
+    const size_t k = j % n;
+    check_i32(seg_ids[j], who, "segment ids");
+    check_i32(seg_count[j], who, "segment count");
+    check_cuda(seg_g[j], "segment g");
+    if (j < n) {
+      TORCH_CHECK(seg_ids[j].numel() < (1LL << 31), who, ": payload capacity");
+      a.nmax.push_back((int)seg_ids[j].numel());
+    }
+    TORCH_CHECK(seg_ids[j].numel() == a.nmax[k] && seg_count[j].numel() >= 1 && seg_g[j].scalar_type() == torch::kFloat32 &&
+                    seg_g[j].is_contiguous() && seg_g[j].numel() >= (int64_t)a.nmax[k] * D[k],
+                who, ": payload sizes");
+    a.ids.push_back(seg_ids[j].data_ptr<int>());
+    a.g.push_back(seg_g[j].data_ptr<float>());
+    a.count.push_back(seg_count[j].data_ptr<int>());
+  }
+  return a;
+}
+
 // apply the gathered segments (segs x n payloads, segment-major) in order; own_seg frees the slots
 void sdp_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> seg_ids, std::vector<torch::Tensor> seg_g,
                std::vector<torch::Tensor> seg_count, std::vector<torch::Tensor> slot, std::vector<torch::Tensor> own_count,
                int64_t segs, int64_t own_seg, torch::Tensor lr) {
   const size_t n = W.size();
   if (n == 0) return;
-  TORCH_CHECK(seg_ids.size() == n * segs && seg_g.size() == n * segs && seg_count.size() == n * segs,
-              "sdp_apply: segs x tables payload views");
   TORCH_CHECK(slot.size() == n && own_count.size() == n, "sdp_apply: slot / own_count per table");
   check_cuda(lr, "lr");
+  TORCH_CHECK(lr.scalar_type() == torch::kFloat32 && lr.numel() >= 1, "lr: fp32 device scalar");
   std::vector<float*> pw;
-  std::vector<int> D, nmax;
-  std::vector<const int*> pi, pn;
-  std::vector<const float*> pg;
+  std::vector<int> D;
   std::vector<int*> ps, po;
   for (size_t k = 0; k < n; ++k) {
     check_cuda(W[k], "W");
     TORCH_CHECK(W[k].scalar_type() == torch::kFloat32 && W[k].is_contiguous() && W[k].dim() == 2, "tables fp32 [rows, D]");
+    check_i32(slot[k], "sdp_apply", "slot");
+    check_i32(own_count[k], "sdp_apply", "own count");
+    TORCH_CHECK(slot[k].numel() >= W[k].size(0) && own_count[k].numel() >= 1, "sdp_apply: slot [rows], own count [1]");
     pw.push_back(W[k].data_ptr<float>());
     D.push_back((int)W[k].size(1));
-    nmax.push_back((int)seg_ids[k].numel());
     ps.push_back(slot[k].data_ptr<int>());
     po.push_back(own_count[k].data_ptr<int>());
   }
-  for (size_t j = 0; j < n * segs; ++j) {
-    const size_t k = j % n;
-    TORCH_CHECK(seg_ids[j].numel() == nmax[k] && seg_g[j].numel() >= (int64_t)nmax[k] * D[k], "sdp_apply: payload sizes");
-    pi.push_back(seg_ids[j].data_ptr<int>());
-    pg.push_back(seg_g[j].data_ptr<float>());
-    pn.push_back(seg_count[j].data_ptr<int>());
-  }
-  fm_sdp_apply_segments((int)n, (int)segs, (int)own_seg, pw.data(), D.data(), pi.data(), pg.data(), pn.data(), ps.data(),
-                        po.data(), nmax.data(), lr.data_ptr<float>(), cur());
+  SegArgs sg = seg_args("sdp_apply", seg_ids, seg_g, seg_count, n, segs, D);
+  fm_sdp_apply_segments((int)n, (int)segs, (int)own_seg, pw.data(), D.data(), sg.ids.data(), sg.g.data(), sg.count.data(),
+                        ps.data(), po.data(), sg.nmax.data(), lr.data_ptr<float>(), cur());
 }
 
-// fused sparse Adagrad (embedding.hip): one coalesced payload (ids, g, count) per table ->
-// H[ids] += g g, W[ids] -= lr g / (sqrt(H[ids]) + eps); frees the slots and zeroes the counts
-void emb_adagrad_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> H, std::vector<torch::Tensor> ids,
-                       std::vector<torch::Tensor> g, std::vector<torch::Tensor> count, std::vector<torch::Tensor> slot,
-                       torch::Tensor lr, double eps) {
+// one coalesced payload (ids, g, count) and the claim slots per table, as the Adagrad apply launchers
+// take them; who = the optimizer's name in the messages
+struct PayloadArgs {
+  std::vector<float*> W, H;
+  std::vector<int> D, nmax;
+  std::vector<const int*> ids;
+  std::vector<const float*> g;
+  std::vector<int*> count, slot;
+};
+
+PayloadArgs payload_args(const char* who, const std::vector<torch::Tensor>& W, const std::vector<torch::Tensor>& H,
+                         const std::vector<torch::Tensor>& ids, const std::vector<torch::Tensor>& g,
+                         const std::vector<torch::Tensor>& count, const std::vector<torch::Tensor>& slot,
+                         const torch::Tensor& lr) {
   const size_t n = W.size();
-  if (n == 0) return;
-  TORCH_CHECK(H.size() == n && ids.size() == n && g.size() == n && count.size() == n && slot.size() == n,
-              "emb_adagrad_apply: one buffer of each kind per table");
+  TORCH_CHECK(H.size() == n && ids.size() == n && g.size() == n && count.size() == n && slot.size() == n, who,
+              ": one buffer of each kind per table");
   check_cuda(lr, "lr");
   TORCH_CHECK(lr.scalar_type() == torch::kFloat32 && lr.numel() >= 1, "lr: fp32 device scalar");
-  std::vector<float*> pw, ph;
-  std::vector<int> D, nmax;
-  std::vector<const int*> pi;
-  std::vector<const float*> pg;
-  std::vector<int*> pn, ps;
+  PayloadArgs a;
   for (size_t k = 0; k < n; ++k) {
     check_cuda(W[k], "W");
     check_cuda(H[k], "H");
@@ -604,27 +638,37 @@ void emb_adagrad_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> 
     check_cuda(count[k], "count");
     check_cuda(slot[k], "slot");
     TORCH_CHECK(W[k].scalar_type() == torch::kFloat32 && W[k].is_contiguous() && W[k].dim() == 2, "tables fp32 [rows, D]");
-    TORCH_CHECK(H[k].scalar_type() == torch::kFloat32 && H[k].is_contiguous() && H[k].sizes() == W[k].sizes(),
-                "adagrad H: fp32, the table's shape");
-    TORCH_CHECK(ids[k].scalar_type() == torch::kInt32 && ids[k].is_contiguous(), "adagrad ids: int32 [nmax]");
-    TORCH_CHECK(ids[k].numel() < (1LL << 31), "adagrad ids: too many lookups");
+    TORCH_CHECK(H[k].scalar_type() == torch::kFloat32 && H[k].is_contiguous(), who, " H: contiguous fp32");
+    TORCH_CHECK(ids[k].scalar_type() == torch::kInt32 && ids[k].is_contiguous(), who, " ids: int32 [nmax]");
+    TORCH_CHECK(ids[k].numel() < (1LL << 31), who, " ids: too many lookups");
     TORCH_CHECK(g[k].scalar_type() == torch::kFloat32 && g[k].is_contiguous() &&
                     g[k].numel() >= ids[k].numel() * W[k].size(1),
-                "adagrad g: fp32 [nmax, D]");
-    TORCH_CHECK(count[k].scalar_type() == torch::kInt32 && count[k].numel() >= 1, "adagrad count: int32 [1]");
-    TORCH_CHECK(slot[k].scalar_type() == torch::kInt32 && slot[k].is_contiguous() && slot[k].numel() >= W[k].size(0),
-                "adagrad slot: int32 [rows]");
-    pw.push_back(W[k].data_ptr<float>());
-    ph.push_back(H[k].data_ptr<float>());
-    D.push_back((int)W[k].size(1));
-    nmax.push_back((int)ids[k].numel());
-    pi.push_back(ids[k].data_ptr<int>());
-    pg.push_back(g[k].data_ptr<float>());
-    pn.push_back(count[k].data_ptr<int>());
-    ps.push_back(slot[k].data_ptr<int>());
+                who, " g: fp32 [nmax, D]");
+    TORCH_CHECK(count[k].scalar_type() == torch::kInt32 && count[k].numel() >= 1, who, " count: int32 [1]");
+    TORCH_CHECK(slot[k].scalar_type() == torch::kInt32 && slot[k].is_contiguous() && slot[k].numel() >= W[k].size(0), who,
+                " slot: int32 [rows]");
+    a.W.push_back(W[k].data_ptr<float>());
+    a.H.push_back(H[k].data_ptr<float>());
+    a.D.push_back((int)W[k].size(1));
+    a.nmax.push_back((int)ids[k].numel());
+    a.ids.push_back(ids[k].data_ptr<int>());
+    a.g.push_back(g[k].data_ptr<float>());
+    a.count.push_back(count[k].data_ptr<int>());
+    a.slot.push_back(slot[k].data_ptr<int>());
   }
-  fm_emb_adagrad_apply((int)n, pw.data(), ph.data(), D.data(), pi.data(), pg.data(), pn.data(), ps.data(), nmax.data(),
-                       lr.data_ptr<float>(), (float)eps, cur());
+  return a;
+}
+
+// fused sparse Adagrad (embedding.hip): one coalesced payload (ids, g, count) per table ->
+// H[ids] += g g, W[ids] -= lr g / (sqrt(H[ids]) + eps); frees the slots and zeroes the counts
+void emb_adagrad_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> H, std::vector<torch::Tensor> ids,
+                       std::vector<torch::Tensor> g, std::vector<torch::Tensor> count, std::vector<torch::Tensor> slot,
+                       torch::Tensor lr, double eps) {
+  if (W.empty()) return;
+  PayloadArgs a = payload_args("adagrad", W, H, ids, g, count, slot, lr);
+  for (size_t k = 0; k < W.size(); ++k) TORCH_CHECK(H[k].sizes() == W[k].sizes(), "adagrad H: fp32, the table's shape");
+  fm_emb_adagrad_apply((int)W.size(), a.W.data(), a.H.data(), a.D.data(), a.ids.data(), a.g.data(), a.count.data(),
+                       a.slot.data(), a.nmax.data(), lr.data_ptr<float>(), (float)eps, cur());
 }
 
 // fused sparse row-wise Adagrad (embedding.hip): one coalesced payload (ids, g, count) per table ->
@@ -633,47 +677,12 @@ void emb_adagrad_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> 
 void emb_rowwise_adagrad_apply(std::vector<torch::Tensor> W, std::vector<torch::Tensor> H, std::vector<torch::Tensor> ids,
                                std::vector<torch::Tensor> g, std::vector<torch::Tensor> count,
                                std::vector<torch::Tensor> slot, torch::Tensor lr, double eps) {
-  const size_t n = W.size();
-  if (n == 0) return;
-  TORCH_CHECK(H.size() == n && ids.size() == n && g.size() == n && count.size() == n && slot.size() == n,
-              "emb_rowwise_adagrad_apply: one buffer of each kind per table");
-  check_cuda(lr, "lr");
-  TORCH_CHECK(lr.scalar_type() == torch::kFloat32 && lr.numel() >= 1, "lr: fp32 device scalar");
-  std::vector<float*> pw, ph;
-  std::vector<int> D, nmax;
-  std::vector<const int*> pi;
-  std::vector<const float*> pg;
-  std::vector<int*> pn, ps;
-  for (size_t k = 0; k < n; ++k) {
-    check_cuda(W[k], "W");
-    check_cuda(H[k], "H");
-    check_cuda(ids[k], "ids");
-    check_cuda(g[k], "g");
-    check_cuda(count[k], "count");
-    check_cuda(slot[k], "slot");
-    TORCH_CHECK(W[k].scalar_type() == torch::kFloat32 && W[k].is_contiguous() && W[k].dim() == 2, "tables fp32 [rows, D]");
-    TORCH_CHECK(H[k].scalar_type() == torch::kFloat32 && H[k].is_contiguous() && H[k].dim() == 2 &&
-                    H[k].size(0) == W[k].size(0) && H[k].size(1) == 1,
-                "rowwise adagrad H: fp32 [rows, 1]");
-    TORCH_CHECK(ids[k].scalar_type() == torch::kInt32 && ids[k].is_contiguous(), "rowwise adagrad ids: int32 [nmax]");
-    TORCH_CHECK(ids[k].numel() < (1LL << 31), "rowwise adagrad ids: too many lookups");
-    TORCH_CHECK(g[k].scalar_type() == torch::kFloat32 && g[k].is_contiguous() &&
-                    g[k].numel() >= ids[k].numel() * W[k].size(1),
-                "rowwise adagrad g: fp32 [nmax, D]");
-    TORCH_CHECK(count[k].scalar_type() == torch::kInt32 && count[k].numel() >= 1, "rowwise adagrad count: int32 [1]");
-    TORCH_CHECK(slot[k].scalar_type() == torch::kInt32 && slot[k].is_contiguous() && slot[k].numel() >= W[k].size(0),
-                "rowwise adagrad slot: int32 [rows]");
-    pw.push_back(W[k].data_ptr<float>());
-    ph.push_back(H[k].data_ptr<float>());
-    D.push_back((int)W[k].size(1));
-    nmax.push_back((int)ids[k].numel());
-    pi.push_back(ids[k].data_ptr<int>());
-    pg.push_back(g[k].data_ptr<float>());
-    pn.push_back(count[k].data_ptr<int>());
-    ps.push_back(slot[k].data_ptr<int>());
-  }
-  fm_emb_rowwise_adagrad_apply((int)n, pw.data(), ph.data(), D.data(), pi.data(), pg.data(), pn.data(), ps.data(),
-                               nmax.data(), lr.data_ptr<float>(), (float)eps, cur());
+  if (W.empty()) return;
+  PayloadArgs a = payload_args("rowwise adagrad", W, H, ids, g, count, slot, lr);
+  for (size_t k = 0; k < W.size(); ++k)
+    TORCH_CHECK(H[k].dim() == 2 && H[k].size(0) == W[k].size(0) && H[k].size(1) == 1, "rowwise adagrad H: fp32 [rows, 1]");
+  fm_emb_rowwise_adagrad_apply((int)W.size(), a.W.data(), a.H.data(), a.D.data(), a.ids.data(), a.g.data(), a.count.data(),
+                               a.slot.data(), a.nmax.data(), lr.data_ptr<float>(), (float)eps, cur());
 }
 
 // replicated tables under row-wise Adagrad: free the own claims (own_ids / own_count, zeroed), then
@@ -686,26 +695,20 @@ void sdp_rowwise_merge(std::vector<torch::Tensor> seg_ids, std::vector<torch::Te
                        std::vector<int64_t> Ds, int64_t segs) {
   const size_t n = slot.size();
   if (n == 0) return;
-  TORCH_CHECK(segs >= 1 && seg_ids.size() == n * segs && seg_g.size() == n * segs && seg_count.size() == n * segs,
-              "sdp_rowwise_merge: segs x tables payload views");
+  const char* who = "sdp_rowwise_merge";
   TORCH_CHECK(own_ids.size() == n && own_count.size() == n && mids.size() == n && mg.size() == n && mcount.size() == n &&
                   Ds.size() == n,
               "sdp_rowwise_merge: one buffer of each kind per table");
-  std::vector<int> rows, D, nmax, mcap;
-  std::vector<const int*> pi, pn, poi;
-  std::vector<const float*> pg;
+  std::vector<int> rows, D, mcap;
+  std::vector<const int*> poi;
   std::vector<int*> ps, po, pmi, pmc;
   std::vector<float*> pmg;
-  auto i32 = [](const torch::Tensor& t, const char* what) {
-    check_cuda(t, what);
-    TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.is_contiguous(), what, ": contiguous int32");
-  };
   for (size_t k = 0; k < n; ++k) {
-    i32(slot[k], "merge slot");
-    i32(own_ids[k], "merge own ids");
-    i32(own_count[k], "merge own count");
-    i32(mids[k], "merge mids");
-    i32(mcount[k], "merge mcount");
+    check_i32(slot[k], who, "slot");
+    check_i32(own_ids[k], who, "own ids");
+    check_i32(own_count[k], who, "own count");
+    check_i32(mids[k], who, "mids");
+    check_i32(mcount[k], who, "mcount");
     check_cuda(mg[k], "merge mg");
     TORCH_CHECK(Ds[k] >= 1 && slot[k].numel() >= 1 && slot[k].numel() < (1LL << 31), "sdp_rowwise_merge: table shape");
     TORCH_CHECK(own_count[k].numel() >= 1 && mcount[k].numel() >= 1, "sdp_rowwise_merge: counts int32 [1]");
@@ -719,7 +722,6 @@ void sdp_rowwise_merge(std::vector<torch::Tensor> seg_ids, std::vector<torch::Te
                 "sdp_rowwise_merge mg: fp32 [mcap, D]");
     rows.push_back((int)slot[k].numel());
     D.push_back((int)Ds[k]);
-    nmax.push_back((int)own_ids[k].numel());
     mcap.push_back((int)mids[k].numel());
     ps.push_back(slot[k].data_ptr<int>());
     poi.push_back(own_ids[k].data_ptr<int>());
@@ -728,20 +730,12 @@ void sdp_rowwise_merge(std::vector<torch::Tensor> seg_ids, std::vector<torch::Te
     pmc.push_back(mcount[k].data_ptr<int>());
     pmg.push_back(mg[k].data_ptr<float>());
   }
-  for (size_t j = 0; j < n * segs; ++j) {
-    const size_t k = j % n;
-    i32(seg_ids[j], "merge segment ids");
-    i32(seg_count[j], "merge segment count");
-    check_cuda(seg_g[j], "merge segment g");
-    TORCH_CHECK(seg_ids[j].numel() == nmax[k] && seg_count[j].numel() >= 1 && seg_g[j].scalar_type() == torch::kFloat32 &&
-                    seg_g[j].is_contiguous() && seg_g[j].numel() >= (int64_t)nmax[k] * D[k],
-                "sdp_rowwise_merge: payload sizes");
-    pi.push_back(seg_ids[j].data_ptr<int>());
-    pg.push_back(seg_g[j].data_ptr<float>());
-    pn.push_back(seg_count[j].data_ptr<int>());
-  }
-  fm_sdp_rowwise_merge_segments((int)n, (int)segs, rows.data(), D.data(), pi.data(), pg.data(), pn.data(), poi.data(),
-                                po.data(), ps.data(), pmi.data(), pmg.data(), pmc.data(), nmax.data(), mcap.data(), cur());
+  SegArgs sg = seg_args(who, seg_ids, seg_g, seg_count, n, segs, D);
+  for (size_t k = 0; k < n; ++k)      // the own payload is one of the segments before the all-gather
+    TORCH_CHECK(own_ids[k].numel() == sg.nmax[k], "sdp_rowwise_merge: payload sizes");
+  fm_sdp_rowwise_merge_segments((int)n, (int)segs, rows.data(), D.data(), sg.ids.data(), sg.g.data(), sg.count.data(),
+                                poi.data(), po.data(), ps.data(), pmi.data(), pmg.data(), pmc.data(), sg.nmax.data(),
+                                mcap.data(), cur());
 }
 
 // dst[to + sum i_k ts_k] (+)= src[so + sum i_k ss_k] over the box d[4] (element offsets / strides

@@ -653,10 +653,14 @@ __global__ void __launch_bounds__(256) fm_sdp_apply(SdpApplySet s, const float* 
   }
 }
 
-// zero the own counts once every segment has been applied (a separate tiny launch: the own
-// segment's count may be read by later segments' launches only through the gathered copy)
-__global__ void fm_sdp_reset_counts(SdpApplySet s) {
-  if (threadIdx.x < s.n && s.t[threadIdx.x].own_count) *s.t[threadIdx.x].own_count = 0;
+// zero per-table counts once the launches before it on the stream have read them (a separate tiny
+// launch of MAXT threads or more: the sparse-DP own segment's count may be read by later segments'
+// launches only through the gathered copy); null entries are skipped
+struct CountSet {
+  int* c[MAXT] = {};
+};
+__global__ void fm_emb_zero_counts(CountSet s) {
+  if (threadIdx.x < MAXT && s.c[threadIdx.x]) *s.c[threadIdx.x] = 0;
 }
 
 // ---- fused sparse Adagrad for non-replicated tables ---------------------------------------------
@@ -669,13 +673,14 @@ __global__ void fm_sdp_reset_counts(SdpApplySet s) {
 // 16-B accesses (D = 128: 32 lanes, two rows per wave) and two rows in flight per lane -- the
 // second one's address is clamped to the last payload row and only its stores are predicated, so
 // the loads of an iteration stay unconditional.  Other D: one wave per row, lane = column.
-// (Row-wise Adagrad -- one accumulator per row -- is a different optimizer: see below.)
+// (Row-wise Adagrad -- one accumulator per row -- is a different optimizer: see below.  Both apply
+// kernels take this descriptor.)
 struct AdaDesc {
   float* W;           // [rows][D] table shard
-  float* H;           // [rows][D] accumulator, same shape
+  float* H;           // accumulator: [rows][D] (element-wise) or [rows] (row-wise)
   const int* ids;     // [nmax] unique local rows      (payload)
   const float* g;     // [nmax][D] summed gradients   (payload)
-  int* count;         // [1] unique rows; zeroed by fm_emb_adagrad_reset after the apply
+  int* count;         // [1] unique rows; zeroed by fm_emb_zero_counts after the apply
   int* slot;          // [rows] claim slots, freed (-1) here
   int D, nmax, vec;
 };
@@ -746,11 +751,6 @@ __global__ void __launch_bounds__(256) fm_emb_adagrad_apply_multi(AdaSet s, cons
   }
 }
 
-// zero the counts once the apply has read them (a separate tiny launch, as fm_sdp_reset_counts)
-__global__ void fm_emb_adagrad_reset(AdaSet s) {
-  if (threadIdx.x < s.n) *s.t[threadIdx.x].count = 0;
-}
-
 // ---- fused sparse row-wise Adagrad ---------------------------------------------------------------
 // One fp32 accumulator per table row ("exact row-wise Adagrad"), applied to a coalesced payload:
 //   h[r] += (1/D) sum_c g[u][c]^2;  W[r][c] -= lr g[u][c] / (sqrt(h[r]) + eps)     (r = ids[u], u < count)
@@ -766,24 +766,10 @@ __global__ void fm_emb_adagrad_reset(AdaSet s) {
 // clamped row as in the element-wise kernel measured slower (39.9 vs 36.0 us,
 // profiles/emb_rowwise_adagrad_ab.txt).  One lane writes h[r] and frees slot[r].  The summation order depends on D alone, so replicas that
 // apply the same payload values stay bit-identical.
-struct RwDesc {
-  float* W;           // [rows][D] table shard
-  float* h;           // [rows] accumulator, one per row
-  const int* ids;     // [nmax] unique local rows      (payload)
-  const float* g;     // [nmax][D] summed gradients   (payload)
-  int* count;         // [1] unique rows; zeroed by fm_emb_rowwise_reset after the apply
-  int* slot;          // [rows] claim slots, freed (-1) here
-  int D, nmax, vec;
-};
-struct RwSet {
-  RwDesc t[MAXT];
-  int n;
-};
-
 __device__ inline float sumsq4(const f32x4_t v) { return v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]; }
 
-__global__ void __launch_bounds__(256) fm_emb_rowwise_apply_multi(RwSet s, const float* __restrict__ lr_p, float eps) {
-  const RwDesc& d = s.t[blockIdx.y];
+__global__ void __launch_bounds__(256) fm_emb_rowwise_apply_multi(AdaSet s, const float* __restrict__ lr_p, float eps) {
+  const AdaDesc& d = s.t[blockIdx.y];                  // d.H: [rows], one accumulator per row
   const long cnt = min(*d.count, d.nmax);
   if (cnt <= 0) return;                                // uniform across the block
   const float lr = lr_p[0];
@@ -803,7 +789,7 @@ __global__ void __launch_bounds__(256) fm_emb_rowwise_apply_multi(RwSet s, const
       const long r = d.ids[u];
       const f32x4_t gv = *reinterpret_cast<const f32x4_t*>(d.g + u * d.D + c0);
       const f32x4_t w = *reinterpret_cast<const f32x4_t*>(d.W + r * d.D + c0);
-      const float hv = d.h[r];
+      const float hv = d.H[r];
       float ss = col ? sumsq4(gv) : 0.0f;
       for (int c4 = lc + 64; c4 < D4; c4 += 64)        // D > 256: further chunks of this lane
         ss += sumsq4(*reinterpret_cast<const f32x4_t*>(d.g + u * d.D + c4 * 4));
@@ -818,7 +804,7 @@ __global__ void __launch_bounds__(256) fm_emb_rowwise_apply_multi(RwSet s, const
         }
       }
       if (live && lc == 0) {
-        d.h[r] = hn;
+        d.H[r] = hn;
         d.slot[r] = -1;                                // release the claim for the next step
       }
     }
@@ -831,20 +817,15 @@ __global__ void __launch_bounds__(256) fm_emb_rowwise_apply_multi(RwSet s, const
       float ss = 0.0f;
       for (int c = lane; c < d.D; c += 64) ss += gu[c] * gu[c];
       for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
-      const float hn = d.h[r] + ss * invD;
+      const float hn = d.H[r] + ss * invD;
       const float mul = lr / (sqrtf(hn) + eps);
       for (int c = lane; c < d.D; c += 64) w[c] -= mul * gu[c];
       if (lane == 0) {
-        d.h[r] = hn;
+        d.H[r] = hn;
         d.slot[r] = -1;
       }
     }
   }
-}
-
-// zero the counts once the apply has read them (a separate tiny launch, as fm_emb_adagrad_reset)
-__global__ void fm_emb_rowwise_reset(RwSet s) {
-  if (threadIdx.x < s.n) *s.t[threadIdx.x].count = 0;
 }
 
 // ---- replicated tables under row-wise Adagrad: deterministic merge of the gathered segments ------
@@ -877,7 +858,7 @@ struct RwMergeSet {
 };
 struct RwRelease {
   const int* ids;     // own payload
-  int* count;         // own count, zeroed by fm_sdp_rowwise_reset_own
+  int* count;         // own count, zeroed by fm_emb_zero_counts after the release
   int* slot;
   int rows, nmax;
 };
@@ -893,10 +874,6 @@ __global__ void __launch_bounds__(256) fm_sdp_rowwise_release(RwReleaseSet s) {
     const int r = d.ids[u];
     if ((unsigned)r < (unsigned)d.rows) d.slot[r] = -1;
   }
-}
-
-__global__ void fm_sdp_rowwise_reset_own(RwReleaseSet s) {
-  if (threadIdx.x < s.n) *s.t[threadIdx.x].count = 0;
 }
 
 // one wave per segment row (lane = 16-B chunk, or column in the scalar form)
@@ -1064,12 +1041,22 @@ extern "C" void fm_embedding_bwd(const void* idx, int idx64, const void* dy, int
 }
 
 // ---- sparse DP launchers -------------------------------------------------------------------
+template <typename GT, bool I64>
+static void launch_coalesce(const SdpSet& s, dim3 gc, dim3 gw, long B, hipStream_t st) {
+  hipLaunchKernelGGL((fm_sdp_claim<I64>), gc, dim3(256), 0, st, s, B);
+  hipLaunchKernelGGL((fm_sdp_assign<GT, I64>), gw, dim3(256), 0, st, s, B);
+  hipLaunchKernelGGL((fm_sdp_dups<GT, I64>), gw, dim3(256), 0, st, s, B);
+}
+
 // coalesce: this rank's lookups of n replicated tables -> (count, ids, g) payloads
 extern "C" void fm_sdp_coalesce(int n, const void* const* idx, const int* idx64, const void* const* dy, const long* ldg,
                                 const long* lo, const int* rows, const int* D, const int* bag, const float* scale,
                                 int dy_bf16, long B, int* const* slot, int* const* cid, int* const* ids, float* const* g,
                                 int* const* count, hipStream_t st) {
   if (B <= 0 || n <= 0) return;
+  static constexpr decltype(&launch_coalesce<float, false>) launch[2][2] = {      // [dy bf16][idx int64]
+      {launch_coalesce<float, false>, launch_coalesce<float, true>},
+      {launch_coalesce<unsigned short, false>, launch_coalesce<unsigned short, true>}};
   for (int wide = 0; wide < 2; ++wide) {
     std::vector<int> sel;
     for (int k = 0; k < n; ++k)
@@ -1088,25 +1075,7 @@ extern "C" void fm_sdp_coalesce(int n, const void* const* idx, const int* idx64,
       const long ne = B * maxbag;
       dim3 gc((unsigned)std::max<long>(1, std::min<long>((ne + 255) / 256, 1024)), m);
       dim3 gw((unsigned)std::max<long>(1, std::min<long>((ne + 3) / 4, 2048)), m);
-      if (wide) {
-        hipLaunchKernelGGL((fm_sdp_claim<true>), gc, dim3(256), 0, st, s, B);
-        if (dy_bf16) {
-          hipLaunchKernelGGL((fm_sdp_assign<unsigned short, true>), gw, dim3(256), 0, st, s, B);
-          hipLaunchKernelGGL((fm_sdp_dups<unsigned short, true>), gw, dim3(256), 0, st, s, B);
-        } else {
-          hipLaunchKernelGGL((fm_sdp_assign<float, true>), gw, dim3(256), 0, st, s, B);
-          hipLaunchKernelGGL((fm_sdp_dups<float, true>), gw, dim3(256), 0, st, s, B);
-        }
-      } else {
-        hipLaunchKernelGGL((fm_sdp_claim<false>), gc, dim3(256), 0, st, s, B);
-        if (dy_bf16) {
-          hipLaunchKernelGGL((fm_sdp_assign<unsigned short, false>), gw, dim3(256), 0, st, s, B);
-          hipLaunchKernelGGL((fm_sdp_dups<unsigned short, false>), gw, dim3(256), 0, st, s, B);
-        } else {
-          hipLaunchKernelGGL((fm_sdp_assign<float, false>), gw, dim3(256), 0, st, s, B);
-          hipLaunchKernelGGL((fm_sdp_dups<float, false>), gw, dim3(256), 0, st, s, B);
-        }
-      }
+      launch[dy_bf16 != 0][wide](s, gc, gw, B, st);
     }
   }
 }
@@ -1122,7 +1091,7 @@ extern "C" void fm_sdp_apply_segments(int n, int segs, int own_seg, float* const
     int nm = 1;
     for (int i = 0; i < m; ++i) nm = std::max(nm, nmax[base + i]);
     dim3 grid((unsigned)std::max(1, std::min((nm + 3) / 4, 2048)), m);
-    SdpApplySet last;
+    CountSet zero;     // stays null (nothing zeroed) when own_seg is none of the segments
     for (int sg = 0; sg < segs; ++sg) {
       SdpApplySet s;
       for (int i = 0; i < m; ++i) {
@@ -1130,64 +1099,58 @@ extern "C" void fm_sdp_apply_segments(int n, int segs, int own_seg, float* const
         const bool own = sg == own_seg;
         s.t[i] = SdpApply{W[k], seg_ids[sg * n + k], seg_g[sg * n + k], seg_count[sg * n + k], D[k], own ? slot[k] : nullptr,
                           own ? own_count[k] : nullptr};
+        if (own) zero.c[i] = own_count[k];
       }
       s.n = m;
       hipLaunchKernelGGL(fm_sdp_apply, grid, dim3(256), 0, st, s, lr, nm);
-      if (sg == own_seg) last = s;
     }
-    if (own_seg >= 0 && own_seg < segs) hipLaunchKernelGGL(fm_sdp_reset_counts, dim3(1), dim3(64), 0, st, last);
+    if (own_seg >= 0 && own_seg < segs) hipLaunchKernelGGL(fm_emb_zero_counts, dim3(1), dim3(64), 0, st, zero);
   }
 }
 
-// ---- sparse Adagrad launcher -----------------------------------------------------------------
-// one payload (ids, g, count) per table from fm_sdp_coalesce -> H / W row updates, slots freed,
-// counts zeroed; nmax[k] = capacity of table k's payload (lookups per step)
-extern "C" void fm_emb_adagrad_apply(int n, float* const* W, float* const* H, const int* D, const int* const* ids,
-                                     const float* const* g, int* const* count, int* const* slot, const int* nmax,
-                                     const float* lr, float eps, hipStream_t st) {
+// ---- Adagrad apply launchers ------------------------------------------------------------------
+// one payload (ids, g, count) per table from fm_sdp_coalesce (or the row-wise merge) -> H / W row
+// updates, slots freed, counts zeroed; nmax[k] = capacity of table k's payload.  h_vec: H is read
+// with 16-B accesses too and takes part in the alignment test (element-wise: H has the table's
+// shape; row-wise: one fp32 per row, read as a scalar).
+static void launch_adagrad_apply(void (*kernel)(AdaSet, const float*, float), bool h_vec, int n, float* const* W,
+                                 float* const* H, const int* D, const int* const* ids, const float* const* g,
+                                 int* const* count, int* const* slot, const int* nmax, const float* lr, float eps,
+                                 hipStream_t st) {
   if (n <= 0) return;
   for (size_t base = 0; base < (size_t)n; base += MAXT) {
     const int m = (int)std::min<size_t>(MAXT, n - base);
     AdaSet s;
+    CountSet zero;
     int nm = 1;
     for (int i = 0; i < m; ++i) {
       const int k = (int)base + i;
-      const bool vec = D[k] % 4 == 0 && ((((uintptr_t)W[k]) | ((uintptr_t)H[k]) | ((uintptr_t)g[k])) & 15) == 0;
+      const uintptr_t a = ((uintptr_t)W[k]) | ((uintptr_t)g[k]) | (h_vec ? (uintptr_t)H[k] : 0);
+      const bool vec = D[k] % 4 == 0 && (a & 15) == 0;
       s.t[i] = AdaDesc{W[k], H[k], ids[k], g[k], count[k], slot[k], D[k], nmax[k], vec ? 1 : 0};
+      zero.c[i] = count[k];
       nm = std::max(nm, nmax[k]);
     }
     s.n = m;
-    // >= 4 rows per block-iteration in either form, two in flight per lane in the vector form
+    // >= 4 rows per block-iteration in either form (element-wise: two in flight per lane in the vector form)
     dim3 grid((unsigned)std::max(1, std::min((nm + 7) / 8, 2048)), m);
-    hipLaunchKernelGGL(fm_emb_adagrad_apply_multi, grid, dim3(256), 0, st, s, lr, eps);
-    hipLaunchKernelGGL(fm_emb_adagrad_reset, dim3(1), dim3(64), 0, st, s);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, s, lr, eps);
+    hipLaunchKernelGGL(fm_emb_zero_counts, dim3(1), dim3(64), 0, st, zero);
   }
 }
 
-// ---- row-wise Adagrad launchers --------------------------------------------------------------
-// one payload (ids, g, count) per table -> h / W row updates, slots freed, counts zeroed;
-// h[k] holds one fp32 per table row; nmax[k] = capacity of table k's payload
+extern "C" void fm_emb_adagrad_apply(int n, float* const* W, float* const* H, const int* D, const int* const* ids,
+                                     const float* const* g, int* const* count, int* const* slot, const int* nmax,
+                                     const float* lr, float eps, hipStream_t st) {
+  launch_adagrad_apply(fm_emb_adagrad_apply_multi, true, n, W, H, D, ids, g, count, slot, nmax, lr, eps, st);
+}
+
+// h[k] holds one fp32 per table row
 extern "C" void fm_emb_rowwise_adagrad_apply(int n, float* const* W, float* const* h, const int* D,
                                              const int* const* ids, const float* const* g, int* const* count,
                                              int* const* slot, const int* nmax, const float* lr, float eps,
                                              hipStream_t st) {
-  if (n <= 0) return;
-  for (size_t base = 0; base < (size_t)n; base += MAXT) {
-    const int m = (int)std::min<size_t>(MAXT, n - base);
-    RwSet s;
-    int nm = 1;
-    for (int i = 0; i < m; ++i) {
-      const int k = (int)base + i;
-      const bool vec = D[k] % 4 == 0 && ((((uintptr_t)W[k]) | ((uintptr_t)g[k])) & 15) == 0;
-      s.t[i] = RwDesc{W[k], h[k], ids[k], g[k], count[k], slot[k], D[k], nmax[k], vec ? 1 : 0};
-      nm = std::max(nm, nmax[k]);
-    }
-    s.n = m;
-    // >= 4 rows per block-iteration in either form
-    dim3 grid((unsigned)std::max(1, std::min((nm + 7) / 8, 2048)), m);
-    hipLaunchKernelGGL(fm_emb_rowwise_apply_multi, grid, dim3(256), 0, st, s, lr, eps);
-    hipLaunchKernelGGL(fm_emb_rowwise_reset, dim3(1), dim3(64), 0, st, s);
-  }
+  launch_adagrad_apply(fm_emb_rowwise_apply_multi, false, n, W, h, D, ids, g, count, slot, nmax, lr, eps, st);
 }
 
 // release the own claims, then merge the segs gathered segments (seg_*[sg * n + k]) of n replicated
@@ -1202,15 +1165,17 @@ extern "C" void fm_sdp_rowwise_merge_segments(int n, int segs, const int* rows, 
     const int m = (int)std::min<size_t>(MAXT, n - base);
     int nm = 1;
     RwReleaseSet rs;
+    CountSet zero;
     for (int i = 0; i < m; ++i) {
       const int k = (int)base + i;
       rs.t[i] = RwRelease{own_ids[k], own_count[k], slot[k], rows[k], nmax[k]};
+      zero.c[i] = own_count[k];
       nm = std::max(nm, nmax[k]);
     }
     rs.n = m;
     hipLaunchKernelGGL(fm_sdp_rowwise_release, dim3((unsigned)std::max(1, std::min((nm + 255) / 256, 1024)), m), dim3(256),
                        0, st, rs);
-    hipLaunchKernelGGL(fm_sdp_rowwise_reset_own, dim3(1), dim3(64), 0, st, rs);
+    hipLaunchKernelGGL(fm_emb_zero_counts, dim3(1), dim3(64), 0, st, zero);
     dim3 grid((unsigned)std::max(1, std::min((nm + 3) / 4, 2048)), m);
     for (int sg = 0; sg < segs; ++sg) {
       RwMergeSet s;

@@ -40,6 +40,13 @@ same fp32 operations on every replica) and apply the merged payload, so the repl
 span ranks), host-placed tables, ``weight_decay != 0`` with a table in the model, and replicated
 tables with ``FLEXMI_SPARSE_DP=0``.
 
+Which of these paths trains a table is decided in one function, ``Embedding.table_rule``
+(``flexmi/ops/embedding.py``): it alone reads ``sparse_capable``, ``sparse_dp_capable``,
+``sparse_dp_always``, ``epsilon`` and ``weight_decay`` and answers a ``TableRule`` (kind, epsilon,
+replica set, host placement; the shape of the table's state), ``None`` for the dense path, or the
+reason a placement is rejected.  The executor trains by that answer and the strategy search
+prices it.
+
 Not provided: host-placed tables under either Adagrad, ``lr_decay``, and Adagrad in the native
 C++ engine.
 """
@@ -217,8 +224,8 @@ class RowwiseAdagradOptimizer(AdagradOptimizer):
     sparse_dp_always = True     # whatever the byte comparison of Embedding.sdp_prefer_sparse says
 
     def table_pc_ok(self, op, pc):
-        """Strategy search hook: False for a table placement the executor rejects -- a column
-        split (a row's sum of squares would span ranks)."""
+        """False for a table placement ``Embedding.table_rule`` rejects (its ``colsplit`` input) -- a
+        column split (a row's sum of squares would span ranks)."""
         return op._grid(pc)[1] == 1
 
     def table_state_bytes(self, rows, cols):

@@ -13,9 +13,11 @@ lookup (CAS), duplicates add with atomics, the owner applies a plain 16-B read-m
 other tables use 256-B-contiguous fp32 atomics; tiny tables accumulate in LDS first.
 Under Adagrad (no weight decay, table not replicated) the backward coalesces the lookups into
 (unique row, summed gradient) payloads and updates accumulator and weights of those rows only
-(``adagrad_group``); still no dense gradient, one extra table-sized buffer (the accumulator).
+(``payload_group``); still no dense gradient, one extra table-sized buffer (the accumulator).
 Under row-wise Adagrad every table is trained that way with one accumulator per ROW
-(``rowwise_group``; replicated tables by a merged sparse-DP exchange, ``sdp_apply_rowwise``).
+(replicated tables by a merged sparse-DP exchange, ``sdp_apply_rowwise``).
+How a table is trained is decided in ONE place, :meth:`Embedding.table_rule`, for the executor and
+the strategy search alike; the executor stores the answer (a :class:`TableRule`) in ``op.rule``.
 SOAP: sample split, **column (parameter) split** of the table, whole-table placement
 (``dims=[1,1]``, device k) -- a 100 M-row table fits one MI355X's 288 GB of HBM -- and **row
 split** (flexmi extension of the strategy format: a third internal degree, ``dims=[c, n, r]``):
@@ -28,6 +30,7 @@ from __future__ import annotations
 
 import math
 import os
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -53,6 +56,19 @@ def _cpu_ext():
             m = None
         _CPU_MOD.append(m)
     return _CPU_MOD[0]
+
+class TableRule(NamedTuple):
+    """How one embedding table (shard) is trained when it has no dense gradient; ``op.rule is None``
+    = dense gradient in a sync group.  Decided by :meth:`Embedding.table_rule`."""
+    kind: str                                   # "sgd", "adagrad" or "rowwise"
+    eps: Optional[float] = None                 # the Adagrad forms' epsilon
+    replicas: Optional[Tuple[int, ...]] = None  # sorted replica set of a table trained by sparse DP
+    host: bool = False                          # host-placed table: lookups and sparse SGD on the CPU
+
+    def state_shape(self, rows, cols):
+        """Shape of the table shard's optimizer state ``h``, or None (SGD)."""
+        return {"sgd": None, "adagrad": (rows, cols), "rowwise": (rows, 1)}[self.kind]
+
 
 class SparseDPState:
     """Payload buffers of one replicated embedding group (see :meth:`Embedding.sdp_pack`).
@@ -156,16 +172,13 @@ class Embedding(Op):
             kernel_initializer = UniformInitializer(model._next_seed() if model else 0, -r, r)
         self._add_weight((self.num_entries, self.out_dim), kernel_initializer, "weight")
         self._finish([(input.dims[0], self.out_dim)])
-        # set by the executor when a fused sparse optimizer applies to this table; sparse_dp =
-        # the replica set of a replicated table trained by touched-row exchange
-        self.sparse_sgd = False
-        self.sparse_dp = None
-        # sparse_adagrad = epsilon when the table is trained by the fused sparse Adagrad update
-        # (non-replicated tables; accumulator in ctx.weight_state[0]["h"]), else None
-        self.sparse_adagrad = None
-        # sparse_rowwise = epsilon when the table is trained by row-wise Adagrad (one accumulator per
-        # row, ctx.weight_state[0]["h"] shaped [rows, 1]; replicated tables also carry sparse_dp)
-        self.sparse_rowwise = None
+        # set by the executor (Embedding.table_rule) when a fused sparse optimizer applies to this
+        # table; the Adagrad forms keep their accumulator in ctx.weight_state[0]["h"]
+        self.rule: Optional[TableRule] = None
+
+    @property
+    def host_exec(self):
+        return self.rule is not None and self.rule.host
 
     def splittable_dims(self):
         return {0, 1}
@@ -240,6 +253,10 @@ class Embedding(Op):
             return None
         return m
 
+    def _scale(self, idx):
+        """Factor on every looked-up row / output gradient: AVG divides by the bag size once."""
+        return 1.0 / idx.shape[1] if self.aggr == AggrMode.AGGR_MODE_AVG else 1.0
+
     def forward(self, ctx: OpCtx):
         idx = ctx.inputs[0]
         w = ctx.weights[0]
@@ -247,8 +264,7 @@ class Embedding(Op):
         if ctx.hip:
             Embedding.forward_group([self], [ctx])
         elif self._native_cpu(w, idx, out) is not None:
-            scale = 1.0 / idx.shape[1] if self.aggr == AggrMode.AGGR_MODE_AVG else 1.0
-            _cpu_ext().embedding_fwd(w, idx.contiguous(), out, self._row_lo(ctx), scale)
+            _cpu_ext().embedding_fwd(w, idx.contiguous(), out, self._row_lo(ctx), self._scale(idx))
         else:
             bag = idx.shape[1]
             li, ok = self._local_rows(idx, self._row_lo(ctx), w.shape[0])
@@ -261,53 +277,37 @@ class Embedding(Op):
     def backward(self, ctx: OpCtx):
         idx = ctx.inputs[0]
         dy = ctx.out_grads[0]
-        if self.sparse_adagrad is not None:
-            Embedding.adagrad_group([self], [ctx])
+        if self.rule is not None and self.rule.kind != "sgd":
+            Embedding.payload_group([self], [ctx])
             return
-        if self.sparse_rowwise is not None:
-            Embedding.rowwise_group([self], [ctx])
-            return
-        if self.sparse_sgd:
-            # fused sparse SGD (no dense grad): W[idx] -= lr * dy  (duplicates summed first)
-            scale = 1.0 / idx.shape[1] if self.aggr == AggrMode.AGGR_MODE_AVG else 1.0
-            if ctx.hip:
-                Embedding.backward_group([self], [ctx])
-            elif self._native_cpu(ctx.weights[0], idx, dy) is not None:
-                _cpu_ext().embedding_bwd(ctx.weights[0], idx.contiguous(), dy, self._row_lo(ctx),
-                                         -float(ctx.lr) * scale)
-            else:
-                g = dy.float()
-                if self.aggr == AggrMode.AGGR_MODE_AVG:
-                    g = g / idx.shape[1]
-                bag = idx.shape[1]
-                li, ok = self._local_rows(idx, self._row_lo(ctx), ctx.weights[0].shape[0])
-                gg = g.repeat_interleave(bag, dim=0) * ok.reshape(-1, 1).to(g.dtype)
-                upd = torch.zeros_like(ctx.weights[0])
-                upd.index_add_(0, li.reshape(-1), gg)
-                ctx.weights[0].sub_(ctx.lr.to(upd.dtype) * upd)
-            return
-        dw = ctx.weight_grads[0]
+        # fused sparse SGD (no dense grad): W[idx] -= lr * dy (duplicates summed first); else the
+        # dense gradient accumulates into weight_grads
+        sparse = self.rule is not None
+        table = ctx.weights[0] if sparse else ctx.weight_grads[0]
         if ctx.hip:
             Embedding.backward_group([self], [ctx])
-        elif self._native_cpu(dw, idx, dy) is not None:
-            scale = 1.0 / idx.shape[1] if self.aggr == AggrMode.AGGR_MODE_AVG else 1.0
-            _cpu_ext().embedding_bwd(dw, idx.contiguous(), dy, self._row_lo(ctx), scale)
+        elif self._native_cpu(table, idx, dy) is not None:
+            scale = self._scale(idx)
+            _cpu_ext().embedding_bwd(table, idx.contiguous(), dy, self._row_lo(ctx),
+                                     -float(ctx.lr) * scale if sparse else scale)
         else:
             g = dy.float()
             if self.aggr == AggrMode.AGGR_MODE_AVG:
                 g = g / idx.shape[1]
             bag = idx.shape[1]
-            li, ok = self._local_rows(idx, self._row_lo(ctx), dw.shape[0])
-            dw.index_add_(0, li.reshape(-1), g.repeat_interleave(bag, dim=0) * ok.reshape(-1, 1).to(g.dtype))
+            li, ok = self._local_rows(idx, self._row_lo(ctx), table.shape[0])
+            gg = g.repeat_interleave(bag, dim=0) * ok.reshape(-1, 1).to(g.dtype)
+            if sparse:
+                upd = torch.zeros_like(table).index_add_(0, li.reshape(-1), gg)
+                table.sub_(ctx.lr.to(upd.dtype) * upd)
+            else:
+                table.index_add_(0, li.reshape(-1), gg)
 
     # ---------------------------------------------------------- fused groups
     @staticmethod
     def can_group(a, b, ca, cb):
         """Executor fusion: independent embeddings with the same placement run as ONE launch."""
-        return (ca.outputs[0].dtype == cb.outputs[0].dtype and a.sparse_sgd == b.sparse_sgd
-                and getattr(a, "sparse_adagrad", None) == getattr(b, "sparse_adagrad", None)
-                and getattr(a, "sparse_rowwise", None) == getattr(b, "sparse_rowwise", None)
-                and getattr(a, "sparse_dp", None) == getattr(b, "sparse_dp", None)
+        return (ca.outputs[0].dtype == cb.outputs[0].dtype and a.rule == b.rule
                 and ca.inputs[0].shape[0] == cb.inputs[0].shape[0])
 
     @staticmethod
@@ -318,8 +318,7 @@ class Embedding(Op):
             return
         K.C().embedding_fwd_multi([c.weights[0] for c in ctxs], [c.inputs[0] for c in ctxs],
                                   [c.outputs[0] for c in ctxs], [c.outputs[0].stride(0) for c in ctxs],
-                                  [1.0 / c.inputs[0].shape[1] if op.aggr == AggrMode.AGGR_MODE_AVG else 1.0
-                                   for op, c in zip(ops, ctxs)],
+                                  [op._scale(c.inputs[0]) for op, c in zip(ops, ctxs)],
                                   [Embedding._row_lo(c) for c in ctxs])
 
     @staticmethod
@@ -328,21 +327,18 @@ class Embedding(Op):
             for op, c in zip(ops, ctxs):
                 op.backward(c)
             return
-        if ops[0].sparse_adagrad is not None:
-            Embedding.adagrad_group(ops, ctxs)
+        rule = ops[0].rule          # one rule per group (can_group)
+        if rule is not None and rule.kind != "sgd":
+            Embedding.payload_group(ops, ctxs)
             return
-        if ops[0].sparse_rowwise is not None:
-            Embedding.rowwise_group(ops, ctxs)
-            return
-        scales = [1.0 / c.inputs[0].shape[1] if op.aggr == AggrMode.AGGR_MODE_AVG else 1.0 for op, c in zip(ops, ctxs)]
-        if ops[0].sparse_sgd:
-            tables = [c.weights[0] for c in ctxs]
-            lr = ctxs[0].lr
-        else:
+        scales = [op._scale(c.inputs[0]) for op, c in zip(ops, ctxs)]
+        claim = None
+        if rule is None:
             tables = [c.weight_grads[0] for c in ctxs]   # accumulate (zeroed once per step)
             lr = None
-        claim = None
-        if ops[0].sparse_sgd:
+        else:
+            tables = [c.weights[0] for c in ctxs]
+            lr = ctxs[0].lr
             bufs = [op._claim_buffers(c) for op, c in zip(ops, ctxs)]
             if any(b is not None for b in bufs):
                 claim = []
@@ -369,7 +365,7 @@ class Embedding(Op):
         st = c0.saved.get("sdp")
         if st is None:
             # row-wise Adagrad sums the gathered segments before it squares them: merged buffers
-            cls = SparseRowwiseDPState if ops[0].sparse_rowwise is not None else SparseDPState
+            cls = SparseRowwiseDPState if ops[0].rule.kind == "rowwise" else SparseDPState
             st = cls(ops, ctxs, holders, rank)
             c0.saved["sdp"] = st
         return st
@@ -377,7 +373,7 @@ class Embedding(Op):
     @staticmethod
     def sdp_pack(ops, ctxs, st=None):
         st = st or ctxs[0].saved["sdp"]
-        scales = [1.0 / c.inputs[0].shape[1] if op.aggr == AggrMode.AGGR_MODE_AVG else 1.0 for op, c in zip(ops, ctxs)]
+        scales = [op._scale(c.inputs[0]) for op, c in zip(ops, ctxs)]
         if ctxs[0].hip:
             K.C().sdp_coalesce([c.weights[0] for c in ctxs], [c.inputs[0] for c in ctxs], [c.out_grads[0] for c in ctxs],
                                [c.out_grads[0].stride(0) for c in ctxs], scales, [Embedding._row_lo(c) for c in ctxs],
@@ -401,7 +397,7 @@ class Embedding(Op):
     def sdp_apply(ops, ctxs):
         st = ctxs[0].saved["sdp"]
         lr = ctxs[0].lr
-        if ops[0].sparse_rowwise is not None:
+        if ops[0].rule.kind == "rowwise":
             Embedding.sdp_apply_rowwise(ops, ctxs, st)
             return
         if ctxs[0].hip:
@@ -419,88 +415,61 @@ class Embedding(Op):
                     w.index_add_(0, st.rids[s][k][:n].long(), mlr * st.rg[s][k][:n * D].view(n, D))
 
     # ---------------------------------------------------------- fused sparse Adagrad
-    # Non-replicated tables under AdagradOptimizer (weight_decay == 0): coalesce the step's lookups
-    # into (unique local rows, summed gradients) -- duplicates are summed BEFORE the gradient is
-    # squared -- then update H and W of those rows only.  Untouched rows have gradient 0 and keep H
-    # and W, so this equals dense element-wise Adagrad without a table-sized gradient buffer.
-    # Replicated tables are not handled here (they stay dense); row-wise Adagrad: rowwise_group below.
+    # Element-wise (rule.kind "adagrad": non-replicated tables under AdagradOptimizer, weight_decay
+    # == 0) and row-wise (rule.kind "rowwise": RowwiseAdagradOptimizer, every table): coalesce the
+    # step's lookups into (unique local rows, summed gradients) -- duplicates are summed BEFORE the
+    # gradient is squared -- then update the accumulator and W of those rows only.  Untouched rows
+    # have gradient 0 and keep both, so this equals the dense rule without a table-sized gradient:
+    #   adagrad: H[r,c] += G[r,c]^2,        W[r,c] -= lr G[r,c] / (sqrt(H[r,c]) + eps)
+    #   rowwise: h[r]   += mean_c(G[r,c]^2), W[r,:] -= lr G[r,:] / (sqrt(h[r]) + eps)
+    # Whole tables and row shards apply the payload where it was packed (payload_group).  Replicated
+    # tables stay dense under element-wise Adagrad; under row-wise Adagrad they run pack / all-gather
+    # as sparse DP does and then sdp_apply_rowwise: the R segments are summed per row in
+    # replica-rank order into a merged payload -- BEFORE the square, and by the same fp32 additions
+    # on every replica -- which the same apply consumes, so the replicas' W and h stay bit-identical.
     @staticmethod
-    def adagrad_group(ops, ctxs):
-        c0 = ctxs[0]
-        st = c0.saved.get("adagrad")
-        if st is None:
-            st = c0.saved["adagrad"] = SparseAdagradState(ops, ctxs, c0.rank)
-        Embedding.sdp_pack(ops, ctxs, st)
-        Embedding.adagrad_apply(ops, ctxs, st)
-
-    @staticmethod
-    def adagrad_apply(ops, ctxs, st):
-        lr = ctxs[0].lr
-        H = [c.weight_state[0]["h"] for c in ctxs]
-        if ctxs[0].hip:
-            eps = {float(op.sparse_adagrad) for op in ops}
-            assert len(eps) == 1
-            K.C().emb_adagrad_apply([c.weights[0] for c in ctxs], H, st.ids[0], st.g[0], st.count[0], st.slot, lr,
-                                    eps.pop())
-            return
-        lrf = lr.to(torch.float32)
-        for k, (op, c) in enumerate(zip(ops, ctxs)):
-            w, h = c.weights[0], H[k]
-            n = int(st.count[0][k].item())
-            if n:
-                D = w.shape[1]
-                rows = st.ids[0][k][:n].long()
-                g = st.g[0][k][:n * D].view(n, D)
-                hr = h[rows] + g * g
-                h[rows] = hr
-                w[rows] = w[rows] - lrf * g / (hr.sqrt() + float(op.sparse_adagrad))
-
-    # ---------------------------------------------------------- fused sparse row-wise Adagrad
-    # RowwiseAdagradOptimizer: one accumulator per row, h[r] += mean_c(G[r,c]^2),
-    # W[r,:] -= lr G[r,:] / (sqrt(h[r]) + eps), G = the row's gradient with every duplicate lookup
-    # summed first.  Whole tables and row shards: coalesce, then apply the payload where it was
-    # packed (rowwise_group).  Replicated tables run pack / all-gather as sparse DP does and then
-    # sdp_apply_rowwise: the R segments are summed per row in replica-rank order into a merged
-    # payload -- BEFORE the square, and by the same fp32 additions on every replica -- which the
-    # same apply kernel consumes, so the replicas' W and h stay bit-identical.
-    @staticmethod
-    def _rowwise_eps(ops):
-        eps = {float(op.sparse_rowwise) for op in ops}
-        assert len(eps) == 1
-        return eps.pop()
+    def _adagrad_rule(w, h, rows, g, lrf, eps):
+        """Element-wise Adagrad on unique local ``rows`` with their summed gradients ``g`` [n, D] (torch)."""
+        hr = h[rows] + g * g
+        h[rows] = hr
+        w[rows] = w[rows] - lrf * g / (hr.sqrt() + eps)
 
     @staticmethod
     def _rowwise_rule(w, h, rows, g, lrf, eps):
-        """The rule on unique local ``rows`` with their summed gradients ``g`` [n, D] (torch)."""
+        """Row-wise Adagrad on unique local ``rows`` with their summed gradients ``g`` [n, D] (torch)."""
         hr = h[rows, 0] + (g * g).sum(1) / w.shape[1]
         h[rows, 0] = hr
         w[rows] = w[rows] - lrf * g / (hr.sqrt() + eps).unsqueeze(1)
 
     @staticmethod
-    def rowwise_group(ops, ctxs):
+    def payload_group(ops, ctxs):
         c0 = ctxs[0]
-        st = c0.saved.get("rowwise")
+        st = c0.saved.get("payload")
         if st is None:
-            st = c0.saved["rowwise"] = SparseAdagradState(ops, ctxs, c0.rank)
+            st = c0.saved["payload"] = SparseAdagradState(ops, ctxs, c0.rank)
         Embedding.sdp_pack(ops, ctxs, st)
-        lr = c0.lr
+        Embedding.payload_apply(ops, ctxs, st.ids[0], st.g[0], st.count[0], st.slot)
+
+    @staticmethod
+    def payload_apply(ops, ctxs, ids, g, count, slot):
+        """Apply one (ids, g, count) payload per table by the group's rule (one per group: can_group)."""
+        rule = ops[0].rule
+        lr = ctxs[0].lr
         H = [c.weight_state[0]["h"] for c in ctxs]
-        if c0.hip:
-            K.C().emb_rowwise_adagrad_apply([c.weights[0] for c in ctxs], H, st.ids[0], st.g[0], st.count[0], st.slot,
-                                            lr, Embedding._rowwise_eps(ops))
+        if ctxs[0].hip:
+            apply = K.C().emb_adagrad_apply if rule.kind == "adagrad" else K.C().emb_rowwise_adagrad_apply
+            apply([c.weights[0] for c in ctxs], H, ids, g, count, slot, lr, float(rule.eps))
             return
+        apply = Embedding._adagrad_rule if rule.kind == "adagrad" else Embedding._rowwise_rule
         lrf = lr.to(torch.float32)
-        for k, (op, c) in enumerate(zip(ops, ctxs)):
-            n = int(st.count[0][k].item())
+        for k, c in enumerate(ctxs):
+            n = int(count[k].item())
             if n:
                 D = c.weights[0].shape[1]
-                Embedding._rowwise_rule(c.weights[0], H[k], st.ids[0][k][:n].long(), st.g[0][k][:n * D].view(n, D),
-                                        lrf, float(op.sparse_rowwise))
+                apply(c.weights[0], H[k], ids[k][:n].long(), g[k][:n * D].view(n, D), lrf, float(rule.eps))
 
     @staticmethod
     def sdp_apply_rowwise(ops, ctxs, st):
-        lr = ctxs[0].lr
-        H = [c.weight_state[0]["h"] for c in ctxs]
         if ctxs[0].hip:
             # release the own claims, merge the segments in rank order, apply the merged payload
             K.C().sdp_rowwise_merge([t for s in range(st.R) for t in st.rids[s]],
@@ -508,23 +477,22 @@ class Embedding(Op):
                                     [t for s in range(st.R) for t in st.rcount[s]],
                                     st.ids[st.seg], st.count[st.seg], st.slot, st.mids, st.mg, st.mcount,
                                     [c.weights[0].shape[1] for c in ctxs], st.R)
-            K.C().emb_rowwise_adagrad_apply([c.weights[0] for c in ctxs], H, st.mids, st.mg, st.mcount, st.slot, lr,
-                                            Embedding._rowwise_eps(ops))
+            Embedding.payload_apply(ops, ctxs, st.mids, st.mg, st.mcount, st.slot)
             return
-        lrf = lr.to(torch.float32)
-        for k, (op, c) in enumerate(zip(ops, ctxs)):
-            w = c.weights[0]
-            D = w.shape[1]
+        mids, mg, mcount = [], [], []
+        for k, c in enumerate(ctxs):
+            D = c.weights[0].shape[1]
             ns = [int(st.rcount[s][k].item()) for s in range(st.R)]
-            if not sum(ns):
-                continue
             uniq, inv = torch.unique(torch.cat([st.rids[s][k][:ns[s]].long() for s in range(st.R)]), return_inverse=True)
             summed = torch.zeros((uniq.numel(), D), dtype=torch.float32)
             o = 0
             for s in range(st.R):       # rank order; rows are unique within a segment
                 summed.index_add_(0, inv[o:o + ns[s]], st.rg[s][k][:ns[s] * D].view(ns[s], D))
                 o += ns[s]
-            Embedding._rowwise_rule(w, H[k], uniq, summed, lrf, float(op.sparse_rowwise))
+            mids.append(uniq)
+            mg.append(summed.reshape(-1))
+            mcount.append(torch.tensor(uniq.numel()))
+        Embedding.payload_apply(ops, ctxs, mids, mg, mcount, None)
 
     CLAIM = True                 # owner-computes path for mostly-unique tables (tests may switch it)
     # owner-computes when rows exceed CLAIM_RATIO x lookups per step (few enough duplicates for the
@@ -575,10 +543,69 @@ class Embedding(Op):
         all-reduce of the table's rows x D gradient.  A ring all-gather of R payloads moves what a
         ring all-reduce of R * payload / 2 words moves, so sparse wins iff R * payload / 2 < rows * D.
         The tiny Criteo tables (3..10 rows) stay dense; 1e5+-row tables go sparse.  One rule for
-        the executor (Executor._build_weights) and the search's cost model (SimGraph._cand)."""
+        the executor and the search's cost model, both through :meth:`table_rule`."""
         if R <= 1:
             return True
         return R * Embedding.sdp_payload_words(lookups, D) / 2.0 < float(rows) * D
+
+    @staticmethod
+    def table_rule(optimizer, rows, cols, lookups, holders, host=False, colsplit=False, sparse_dp=True):
+        """How a table shard of ``rows x cols`` held by ``holders`` (R = their number, the shard's
+        replication; ``lookups`` per replica and step) is trained: ``(rule, None)`` with ``rule`` a
+        :class:`TableRule` or None (dense gradient in a sync group), or ``(None, why)`` for a
+        placement that cannot be trained.  ``host``: host-placed; ``colsplit``: the table's columns
+        are split over ranks; ``sparse_dp``: sparse data parallelism is enabled.  A sparse update
+        needs the optimizer's step on an untouched row to be the identity (``sparse_capable``).  The
+        ONE place that reads the optimizers' sparse-path attributes: Executor._build_weights trains
+        by the answer and SimGraph._cand prices it, both via :meth:`shard_rule`."""
+        R = len(holders)
+        replicas = tuple(sorted(holders)) if R > 1 else None
+        if getattr(optimizer, "sparse_dp_always", False):
+            # row-wise Adagrad: a table has no dense path, so what the sparse one cannot do is rejected
+            why = None
+            if host:
+                why = "host-placed tables (device_type=CPU) are not supported"
+            elif colsplit:       # what the optimizer's search hook table_pc_ok answers False to
+                why = "column-split tables are not supported (a row's sum of squares would span ranks)"
+            elif optimizer.weight_decay != 0.0:
+                why = "weight_decay != 0 is not supported with embedding tables (a table has no dense path)"
+            elif R > 1 and not sparse_dp:
+                why = "replicated tables need sparse data parallelism (FLEXMI_SPARSE_DP=0 is set)"
+            if why:
+                return None, "row-wise Adagrad: " + why
+            return TableRule("rowwise", optimizer.epsilon, replicas), None
+        sparse = bool(getattr(optimizer, "sparse_capable", False))
+        sgd = sparse and not hasattr(optimizer, "epsilon")     # plain SGD; else Adagrad without weight decay
+        if host:
+            if sgd:
+                return TableRule("sgd", host=True), None
+            return None, ("CPU placement is supported for embedding tables trained with SGD "
+                          "(the reference's hetero strategy)")
+        if not sparse:
+            return None, None
+        if R > 1:
+            # sparse DP applies the replicas' segments one by one: an SGD form (sparse_dp_capable),
+            # taken where it moves fewer bytes than the dense replica all-reduce
+            if not (optimizer.sparse_dp_capable and sparse_dp and Embedding.sdp_prefer_sparse(rows, cols, lookups, R)):
+                return None, None
+        return (TableRule("sgd", None, replicas) if sgd else TableRule("adagrad", optimizer.epsilon)), None
+
+    def shard_shape(self, lay, part, R):
+        """(rows, cols, lookups per replica and step) of part ``part`` of the weight layout ``lay``
+        replicated over ``R`` holders: the quantities :meth:`table_rule` and the cost model use."""
+        box = lay.part_box(part)
+        rows = max(1, box[0][1] - box[0][0])
+        cols = 1
+        for lo, hi in box[1:]:
+            cols *= hi - lo
+        B = self.inputs[0].dims[0]
+        bag = self.inputs[0].dims[1] if len(self.inputs[0].dims) > 1 else 1
+        return rows, cols, -(-B // R) * bag
+
+    def shard_rule(self, optimizer, pc, lay, part, holders, sparse_dp=True):
+        """:meth:`table_rule` for part ``part`` of this op's weight layout ``lay`` under ``pc``."""
+        return Embedding.table_rule(optimizer, *self.shard_shape(lay, part, len(holders)), holders,
+                                    host=pc.device_type == pc.CPU, colsplit=self._grid(pc)[1] > 1, sparse_dp=sparse_dp)
 
     def bytes_moved(self, in_shapes, out_shapes, elem=2):
         b, bag = in_shapes[0]

@@ -139,17 +139,6 @@ class SimGraph:
         self.cost = cost or CostModel(self.machine, dtype_bytes=2 if model.config.compute_dtype == "bf16" else 4)
         opt = model.optimizer
         self.nstates = len(opt.state_names()) if opt is not None and hasattr(opt, "state_names") else 0
-        self.sparse_ok = bool(getattr(opt, "sparse_capable", False))
-        # sparse data parallelism (replicated tables by touched-row exchange) is an SGD form:
-        # applying the replica segments one by one is not Adagrad of the summed gradient, so a
-        # replicated table under Adagrad is priced dense, as the executor trains it
-        self.sparse_dp_ok = self.sparse_ok and bool(getattr(opt, "sparse_dp_capable", False))
-        # optimizer hooks (row-wise Adagrad): table placements the executor would reject, replicated
-        # tables trained by sparse DP whatever the byte comparison says (no dense alternative), and
-        # the optimizer state of a sparsely trained table shard (one fp32 per row, not per element)
-        self.table_pc_ok = getattr(opt, "table_pc_ok", None)
-        self.sdp_always = self.sparse_dp_ok and bool(getattr(opt, "sparse_dp_always", False))
-        self.table_state_bytes = getattr(opt, "table_state_bytes", None)
         self.ops = list(model.layers)
         md = self.machine.native_dict()
         if not md["xchg_chunks"]:
@@ -173,8 +162,9 @@ class SimGraph:
                 pc = extra[op.name]
                 if op.valid_pc(pc) and max(pc.device_ids) < ndev and pc not in cl:
                     cl.append(pc)
-            if self.table_pc_ok is not None and op.op_type == OperatorType.OP_EMBEDDING:
-                keep = [pc for pc in cl if self.table_pc_ok(op, pc)]
+            if op.op_type == OperatorType.OP_EMBEDDING:
+                # column splits the optimizer cannot train (row-wise Adagrad: Embedding.table_rule)
+                keep = [pc for pc in cl if op._grid(pc)[1] == 1 or self._rule(op, pc, op.weight_layouts(pc)[0], 0)[1] is None]
                 if keep:            # dropped only while a candidate remains
                     cl = keep
             self.cands.append(cl)
@@ -184,8 +174,12 @@ class SimGraph:
     def _eb(self, t):
         return self.cost.eb if t.data_type in _FLOAT else 8
 
+    def _rule(self, op, pc, lay, p):
+        """(rule, why) of part ``p`` of an embedding table's weight layout (Embedding.table_rule).  The
+        search prices sparse data parallelism as enabled (it does not read FLEXMI_SPARSE_DP)."""
+        return op.shard_rule(self.model.optimizer, pc, lay, p, lay.holders[p])
+
     def _cand(self, op, pc: ParallelConfig):
-        from flexmi.ops.embedding import Embedding
         outs = op.output_layouts(pc)
         ins = op.input_layouts(pc)
         wls = op.weight_layouts(pc)
@@ -208,54 +202,35 @@ class SimGraph:
             for p in range(lay.num_parts()):
                 vol = _prod(_box_shape(lay.part_box(p)))
                 h = lay.holders[p]
-                sparse = emb and self.sparse_ok
+                # how the executor trains this table shard: the one rule of both (Embedding.table_rule);
+                # a placement it rejects cannot run and is priced dense
+                rule = None
+                if emb:
+                    rows, cols, lookups = op.shard_shape(lay, p, len(h))
+                    rule = self._rule(op, pc, lay, p)[0]
                 sdp_words = 0.0
-                if sparse and len(h) > 1 and not self.sparse_dp_ok:
-                    sparse = False
-                if sparse and len(h) > 1:
-                    # the executor's per-table rule (Executor._sdp_pays): sparse DP only where the
-                    # touched-row all-gather moves fewer bytes than the dense replica all-reduce
-                    R = len(h)
-                    B = op.inputs[0].dims[0]
-                    bag = op.inputs[0].dims[1] if len(op.inputs[0].dims) > 1 else 1
-                    box = lay.part_box(p)
-                    rows = max(1, box[0][1] - box[0][0])
-                    lookups = -(-B // R) * bag
-                    sparse = self.sdp_always or Embedding.sdp_prefer_sparse(rows, vol // rows, lookups, R)
-                    if sparse:
-                        sdp_words = float(R * op.sdp_payload_words(lookups, vol // rows))
-                        if self.sdp_always:     # + the merged payload the R segments are summed into
-                            sdp_words += float(min(rows, R * lookups) * (vol // rows + 1))
                 if len(h) > 1:
-                    if sparse:
+                    if rule is not None:
                         # replicated table with the sparse optimizer = the executor's sparse data
                         # parallelism (Embedding.sdp_*): every replica all-gathers a fixed payload of
                         # its sample shard's lookups -- count + ids + fp32 row gradients, padded to
                         # one slot per lookup -- and applies all R segments.  A ring all-gather of
                         # R payloads moves what a ring all-reduce of R*payload/2 bytes moves.
                         R = len(h)
-                        B = op.inputs[0].dims[0]
-                        bag = op.inputs[0].dims[1] if len(op.inputs[0].dims) > 1 else 1
-                        box = lay.part_box(p)
-                        cols = vol // max(1, box[0][1] - box[0][0])
-                        lookups = -(-B // R) * bag
-                        payload = 4.0 * op.sdp_payload_words(lookups, cols)
-                        wsync.append((R * payload / 2.0, list(h)))
+                        sdp_words = float(R * op.sdp_payload_words(lookups, cols))
+                        wsync.append((4.0 * sdp_words / 2.0, list(h)))
+                        if rule.kind == "rowwise":     # + the merged payload the R segments are summed into
+                            sdp_words += float(min(rows, R * lookups) * (cols + 1))
                         for d in h:   # the apply: R segments of row read-modify-writes
-                            upd_bytes[d] = upd_bytes.get(d, 0.0) + float(min(vol, B * bag * cols)) * 4.0
+                            upd_bytes[d] = upd_bytes.get(d, 0.0) + float(min(vol, _prod(op.inputs[0].dims) * cols)) * 4.0
                     else:
                         wsync.append((float(vol * 4), list(h)))
                 for d in h:
-                    if sparse:
-                        # the table + (sparse DP) the R-slot receive buffer of the all-gather +
-                        # one table-sized buffer per optimizer state (sparse Adagrad: h; row-wise
+                    if rule is not None:
+                        # the table + (sparse DP) the R-slot receive buffer of the all-gather + the
+                        # rule's optimizer state (sparse Adagrad: h of the table's shape; row-wise
                         # Adagrad: one fp32 per row)
-                        if self.table_state_bytes is not None:
-                            box = lay.part_box(p)
-                            rows = max(1, box[0][1] - box[0][0])
-                            state_b = float(self.table_state_bytes(rows, vol // rows))
-                        else:
-                            state_b = vol * 4.0 * self.nstates
+                        state_b = 4.0 * _prod(rule.state_shape(rows, cols) or (0,))
                         mem[d] = mem.get(d, 0.0) + vol * 4.0 + state_b + sdp_words * 4.0
                     else:
                         mem[d] = mem.get(d, 0.0) + vol * (4.0 + 4.0 + 2.0 + 4.0 * self.nstates)

@@ -28,7 +28,7 @@ import torch
 
 from flexmi.core.loss_metrics import NUM_SLOTS, PerfMetrics, loss_and_metrics_torch
 from flexmi.core.initializers import _native_cpu
-from flexmi.core.optimizers import AdagradOptimizer, AdamOptimizer, RowwiseAdagradOptimizer, SGDOptimizer
+from flexmi.core.optimizers import AdagradOptimizer, AdamOptimizer, SGDOptimizer
 from flexmi.core.types import DataType, LossType, to_torch_dtype
 from flexmi.ops.base import OpCtx
 from flexmi.parallel.layout import Layout, ParallelConfig, ReshardPlan, box_intersect, box_volume
@@ -1110,50 +1110,9 @@ class Executor:
                     self.group_of[op.guid] = g
 
     # ------------------------------------------------------------------
-    @staticmethod
-    def _sdp_pays(op, lay):
-        """Replicated table: sparse DP (touched-row all-gather) only where it moves fewer bytes
-        than the dense replica all-reduce (Embedding.sdp_prefer_sparse; the search prices the same
-        rule).  Every rank decides from global shapes only, so all replicas agree."""
-        from flexmi.ops.embedding import Embedding
-        R = lay.replication()
-        box = lay.part_box(0)
-        rows = box[0][1] - box[0][0]
-        cols = 1
-        for lo, hi in box[1:]:
-            cols *= hi - lo
-        B = op.inputs[0].dims[0]
-        bag = op.inputs[0].dims[1] if len(op.inputs[0].dims) > 1 else 1
-        return Embedding.sdp_prefer_sparse(rows, cols, -(-B // R) * bag, R)
-
-    def _check_rowwise_table(self, op, pc, lay):
-        """Row-wise Adagrad trains every table sparsely; reject what that path cannot do."""
-        why = None
-        if pc.device_type == ParallelConfig.CPU:
-            why = "host-placed tables (device_type=CPU) are not supported"
-        elif op._grid(pc)[1] > 1:
-            why = "column-split tables are not supported (a row's sum of squares would span ranks)"
-        elif self.optimizer.weight_decay != 0.0:
-            why = "weight_decay != 0 is not supported with embedding tables (a table has no dense path)"
-        elif lay.replication() > 1 and not SPARSE_DP:
-            why = "replicated tables need sparse data parallelism (FLEXMI_SPARSE_DP=0 is set)"
-        if why:
-            raise NotImplementedError(f"{op.name}: row-wise Adagrad: {why}")
-
     def _build_weights(self, ops):
         self.wentries: Dict[int, WeightEntry] = {}
         groups: "OrderedDict[tuple, SyncGroup]" = OrderedDict()
-        sparse_ok = isinstance(self.optimizer, SGDOptimizer) and self.optimizer.sparse_capable
-        # Adagrad without weight decay: non-replicated tables are updated row by row with an
-        # accumulator of the table's shape (Embedding.adagrad_group); replicated tables stay in the
-        # dense groups (the replica all-reduce sums the gradients before they are squared -- sparse
-        # DP would not), and host-placed tables are not supported
-        adagrad_ok = isinstance(self.optimizer, AdagradOptimizer) and self.optimizer.sparse_capable
-        # row-wise Adagrad (checked first: it is a subclass): every table is trained sparsely with
-        # one accumulator per row held (Embedding.rowwise_group), replicated ones by the merged
-        # touched-row exchange (Embedding.sdp_apply_rowwise); a table has no dense path, so what
-        # the sparse path cannot do is rejected here
-        rowwise = isinstance(self.optimizer, RowwiseAdagradOptimizer)
         for op in reversed(ops):  # backward order => buckets fill contiguously
             pc = self.pcs[op.guid]
             lays = op.weight_layouts(pc)
@@ -1164,57 +1123,37 @@ class Executor:
                 e = WeightEntry(w, op, wi, lays[wi], self.rank)
                 self.wentries[w.guid] = e
                 from flexmi.core.types import OperatorType
-                if rowwise and op.op_type == OperatorType.OP_EMBEDDING:
-                    self._check_rowwise_table(op, pc, lays[wi])     # on every rank, holder or not
+                rule = None
+                if op.op_type == OperatorType.OP_EMBEDDING:
+                    # how the table is trained: decided in one place (Embedding.table_rule, which the
+                    # strategy search prices too) from global shapes only -- part 0's rows -- and on
+                    # every rank, holder or not, so all ranks agree and reject alike
+                    rule, why = op.shard_rule(self.optimizer, pc, lays[wi], 0, e.holders or lays[wi].holders[0],
+                                              sparse_dp=SPARSE_DP)
+                    if why:
+                        raise NotImplementedError(f"{op.name}: {why}")
+                elif pc.device_type == ParallelConfig.CPU and e.box is not None:
+                    raise NotImplementedError(f"{op.name}: CPU placement is supported for embedding "
+                                              "tables trained with SGD (the reference's hetero strategy)")
                 if e.box is None:
                     continue
-                if pc.device_type == ParallelConfig.CPU:
-                    # heterogeneous placement (dlrm_strategy_hetero.cc): the table
-                    # lives in (pinned) host memory and its lookups / sparse SGD run on the host
-                    if op.op_type != OperatorType.OP_EMBEDDING or not sparse_ok:
-                        raise NotImplementedError(f"{op.name}: CPU placement is supported for embedding "
-                                                  "tables trained with SGD (the reference's hetero strategy)")
-                    e.sparse = True
-                    op.sparse_sgd = True
-                    op.host_exec = True
-                    e.master = torch.empty(e.shape, dtype=torch.float32, pin_memory=self.backend == "hip")
-                    e.compute = e.master
-                    continue
                 if op.op_type == OperatorType.OP_EMBEDDING:
-                    op.sparse_dp = None
-                    op.sparse_adagrad = None
-                    op.sparse_rowwise = None
-                    if rowwise:
-                        e.sparse = True
-                        op.sparse_sgd = False
-                        op.sparse_rowwise = self.optimizer.epsilon
-                        if lays[wi].replication() > 1:
-                            # no dense alternative, so _sdp_pays is not consulted
-                            op.sparse_dp = tuple(sorted(e.holders))
-                        e.master = self._alloc(e.shape, torch.float32)
-                        e.compute = e.master
-                        e.state = {"h": torch.full((e.shape[0], 1), self.optimizer.state_init("h"), dtype=torch.float32,
-                                                   device=self.device)}
-                        continue
-                    if adagrad_ok and lays[wi].replication() == 1:
-                        e.sparse = True
-                        op.sparse_sgd = False
-                        op.sparse_adagrad = self.optimizer.epsilon
-                        e.master = self._alloc(e.shape, torch.float32)
-                        e.compute = e.master
-                        e.state = {"h": torch.full(e.shape, self.optimizer.state_init("h"), dtype=torch.float32,
-                                                   device=self.device)}
-                        continue
-                if (op.op_type == OperatorType.OP_EMBEDDING and sparse_ok
-                        and (lays[wi].replication() == 1 or (SPARSE_DP and self._sdp_pays(op, lays[wi])))):
-                    # non-replicated: fused sparse SGD; replicated: sparse data parallelism
-                    # (touched-row all-gather over the replica set, Embedding.sdp_*)
+                    op.rule = rule
+                if rule is not None:
+                    # no dense gradient: fused sparse SGD / Adagrad / row-wise Adagrad on the rows a step
+                    # looks up (replicated: sparse data parallelism, Embedding.sdp_*).  A host-placed
+                    # table (heterogeneous placement, SURVEY §2.5 P6, dlrm_strategy_hetero.cc) lives
+                    # in (pinned) host memory and its lookups / sparse SGD run on the host
                     e.sparse = True
-                    op.sparse_sgd = True
-                    if lays[wi].replication() > 1:
-                        op.sparse_dp = tuple(sorted(e.holders))
-                    e.master = self._alloc(e.shape, torch.float32)
+                    if rule.host:
+                        e.master = torch.empty(e.shape, dtype=torch.float32, pin_memory=self.backend == "hip")
+                    else:
+                        e.master = self._alloc(e.shape, torch.float32)
                     e.compute = e.master
+                    hs = rule.state_shape(*e.shape)
+                    if hs is not None:
+                        e.state = {"h": torch.full(hs, self.optimizer.state_init("h"), dtype=torch.float32,
+                                                   device=self.device)}
                     continue
                 key = e.holders
                 if key not in groups:
@@ -1867,7 +1806,7 @@ class Executor:
                             C(bwd, o.name + ".zero_unused_grad", (lambda t=self.grad[o.guid]: t.zero_()))
                             written.add(self.gkey(o.guid))
                     grp = self.group_of.get(op.guid)
-                    if getattr(op, "sparse_dp", None) and (grp is None or grp[0] is op):
+                    if getattr(op, "rule", None) and op.rule.replicas and (grp is None or grp[0] is op):
                         self._emit_sparse_dp(bwd, grp or [op])
                     elif grp is not None:
                         if grp[0] is op:
@@ -1982,7 +1921,7 @@ class Executor:
         ctxs = [self.ctx[o.guid] for o in grp]
         op = grp[0]
         cls = type(op)
-        st = cls.sdp_state(grp, ctxs, op.sparse_dp, self.rank)
+        st = cls.sdp_state(grp, ctxs, op.rule.replicas, self.rank)
         name = op.name + (".group" if len(grp) > 1 else "")
         bwd.append(Item("compute", (lambda grp=grp, ctxs=ctxs: cls.sdp_pack(grp, ctxs)), name + ".sdp_pack"))
         bwd.append(Item("comm", (lambda st=st: st.exchange(self.comm)), name + ".sdp_allgather",

@@ -243,7 +243,11 @@ def test_search_prices_replicated_tables_dense(capsys):
     m = cli._model("dlrm-tiny", 2, 64, True, "adagrad")
     assert isinstance(m.optimizer, AdagradOptimizer)
     g = SimGraph(m, 2)
-    assert g.sparse_ok and not g.sparse_dp_ok
+    from flexmi.ops.embedding import Embedding, TableRule
+    # sparse where the table is not replicated, dense where it is -- even where SGD would go sparse
+    assert Embedding.table_rule(m.optimizer, 100000, 16, 32, (0,)) == (TableRule("adagrad", 1e-10, None), None)
+    assert Embedding.table_rule(m.optimizer, 100000, 16, 32, (0, 1)) == (None, None)
+    assert Embedding.sdp_prefer_sparse(100000, 16, 32, 2)
     n = 0
     for k, op in enumerate(g.ops):
         if op.op_type.name != "OP_EMBEDDING":

@@ -64,6 +64,7 @@ def _steps(m, d, s, first, n):
 
 def _check_entries(m, world):
     from flexmi.core.types import OperatorType
+    from flexmi.ops.embedding import TableRule
     ex = m._ex()
     embs = [e for e in ex.wentries.values() if e.op.op_type == OperatorType.OP_EMBEDDING]
     assert len(embs) == 4
@@ -71,11 +72,11 @@ def _check_entries(m, world):
     for e in embs:
         if e.layout.replication() == 1:
             if e.box is not None:          # this rank holds a shard of the table
-                assert e.op.sparse_adagrad == 1e-10 and e.op.sparse_dp is None
+                assert e.op.rule == TableRule("adagrad", 1e-10, None)
                 assert e.sparse and e.grad is None and e.group is None and id(e) not in in_groups
                 assert set(e.state) == {"h"} and tuple(e.state["h"].shape) == tuple(e.shape)
         else:
-            assert not e.sparse and e.op.sparse_adagrad is None and e.op.sparse_dp is None
+            assert not e.sparse and e.op.rule is None
             assert id(e) in in_groups and e.grad is not None
     return sum(e.layout.replication() > 1 for e in embs)
 

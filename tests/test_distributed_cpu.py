@@ -265,13 +265,24 @@ def _run(case, world, rank, steps, out_path):
         # replica all-reduce (Embedding.sdp_prefer_sparse); the others stay in a dense group
         from flexmi.core.types import OperatorType
         embs = [e for e in ex.wentries.values() if e.op.op_type == OperatorType.OP_EMBEDDING]
-        sp = [e for e in embs if ex._sdp_pays(e.op, e.layout)]
+        from flexmi.ops.embedding import Embedding, TableRule
+
+        def pays(e):        # the rule function on the quantities Executor._build_weights passes it
+            box = e.layout.part_box(0)
+            B, bag = e.op.inputs[0].dims
+            rule, why = Embedding.table_rule(ex.optimizer, box[0][1] - box[0][0], box[1][1] - box[1][0],
+                                             -(-B // world) * bag, e.holders)
+            assert why is None and rule in (None, TableRule("sgd", None, tuple(range(world))))
+            assert (rule is not None) == Embedding.sdp_prefer_sparse(box[0][1] - box[0][0], box[1][1] - box[1][0],
+                                                                     -(-B // world) * bag, e.layout.replication())
+            return rule is not None
+        sp = [e for e in embs if pays(e)]
         dn = [e for e in embs if e not in sp]
         assert sp and all(e.sparse and e.group is None and e.grad is None for e in sp)
-        assert all(e.op.sparse_dp == tuple(range(world)) for e in sp)
+        assert all(e.op.rule == TableRule("sgd", None, tuple(range(world))) for e in sp)
         dense_in_groups = [e for g in ex.groups for e in g.entries if e.op.op_type == OperatorType.OP_EMBEDDING]
         assert sorted(id(e) for e in dense_in_groups) == sorted(id(e) for e in dn)
-        assert all(not e.sparse and e.op.sparse_dp is None for e in dn)
+        assert all(not e.sparse and e.op.rule is None for e in dn)
         if case == "dlrm_dpmix":
             assert [e.shape[0] for e in dn] == [3], [e.shape for e in dn]
         rep = ex.memory_report()

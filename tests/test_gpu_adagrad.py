@@ -176,6 +176,56 @@ def test_apply_rejects_mismatched_buffers(gpu):
         K.C().emb_adagrad_apply([W], [torch.zeros(8, 4, device=dev)], [ids], [g], [cnt], [slot[:4]], lr, EPS)
 
 
+@pytest.mark.parametrize("rule", ["adagrad", "rowwise"])
+def test_more_tables_than_one_launch_holds(gpu, rule):
+    """33 tables: the launchers batch 32 per launch, so the last table runs in a second batch of one
+    (its own descriptor set, apply launch and count-zeroing launch).  D alternates 4 (16-B form) and
+    6 (scalar form); every table sees a duplicate row across bags and one inside a bag."""
+    from flexmi.ops import _kernels as K
+    dev = gpu
+    torch.manual_seed(2)
+    T, rows, B, bag = 33, 8, 4, 2
+    Ds = [4 if k % 2 == 0 else 6 for k in range(T)]
+    W = [torch.randn(rows, D, device=dev) for D in Ds]
+    H = [torch.rand(rows, D if rule == "adagrad" else 1, device=dev) * 0.9 + 0.1 for D in Ds]
+    slot = [torch.full((rows,), -1, dtype=torch.int32, device=dev) for _ in Ds]
+    cid = [torch.empty(B * bag, dtype=torch.int32, device=dev) for _ in Ds]
+    ids = [torch.zeros(B * bag, dtype=torch.int32, device=dev) for _ in Ds]
+    g = [torch.zeros(B * bag * D, dtype=torch.float32, device=dev) for D in Ds]
+    cnt = [torch.zeros(1, dtype=torch.int32, device=dev) for _ in Ds]
+    idx = [torch.tensor([[0, 1], [1, 2], [3, 3], [k % rows, 5]], device=dev) for k in range(T)]
+    dy = [torch.randn(B, D, device=dev) for D in Ds]
+    lr = torch.tensor([LR], device=dev)
+    lr64 = float(lr.item())
+    w64 = [w.double().clone() for w in W]
+    h64 = [h.double().clone() for h in H]
+    w_before = [w.clone() for w in W]
+    h_before = [h.clone() for h in H]
+    K.C().sdp_coalesce(W, idx, dy, [d.stride(0) for d in dy], [0.5] * T, [0] * T, slot, cid, ids, g, cnt)
+    apply = K.C().emb_adagrad_apply if rule == "adagrad" else K.C().emb_rowwise_adagrad_apply
+    apply(W, H, ids, g, cnt, slot, lr, EPS)
+    torch.cuda.synchronize()
+    for k in range(T):
+        uniq, s = _oracle(idx[k], dy[k], rows, 0, 0.5)
+        assert 0 < uniq.numel() < B * bag
+        if rule == "adagrad":
+            h64[k][uniq] += s * s
+            w64[k][uniq] -= lr64 * s / (h64[k][uniq].sqrt() + EPS)
+        else:
+            h64[k][uniq] += (s * s).sum(1, keepdim=True) / Ds[k]
+            w64[k][uniq] -= lr64 * s / (h64[k][uniq].sqrt() + EPS)
+        dup = max(1.0, (B * bag / uniq.numel()) ** 0.5)
+        gmax = float(s.abs().max())
+        torch.testing.assert_close(W[k].double(), w64[k], rtol=1e-5, atol=1e-6 + (LR / 0.1 ** 0.5) * 1e-5 * dup)
+        torch.testing.assert_close(H[k].double(), h64[k], rtol=2e-5, atol=2e-5 * dup * gmax)
+        untouched = torch.ones(rows, dtype=torch.bool, device=dev)
+        untouched[uniq] = False
+        assert torch.equal(W[k][untouched], w_before[k][untouched])
+        assert torch.equal(H[k][untouched], h_before[k][untouched])
+        assert int(cnt[k].item()) == 0, f"table {k}: count not reset"
+        assert int((slot[k] != -1).sum().item()) == 0, f"table {k}: claim slots not released"
+
+
 # ------------------------------------------------------------------ model level
 B_MODEL = 128
 

@@ -11,6 +11,7 @@ import torch
 from flexmi.core import (AdagradOptimizer, AggrMode, DataType, FFConfig, FFModel, LossType, MetricsType,
                          RowwiseAdagradOptimizer, SGDOptimizer)
 from flexmi.core.types import OperatorType
+from flexmi.ops.embedding import TableRule
 
 B = 64
 LR, EPS, H0 = 0.05, 1e-10, 0.1
@@ -92,7 +93,7 @@ def test_tiny_dlrm_matches_dense_torch_reference():
         assert e.sparse and e.grad is None and e.group is None
         assert set(e.state) == {"h"} and tuple(e.state["h"].shape) == (r, 1)
         assert float(e.state["h"].min()) == float(e.state["h"].max()) == pytest.approx(H0)
-        assert e.op.sparse_rowwise == EPS and e.op.sparse_adagrad is None and not e.op.sparse_sgd and e.op.sparse_dp is None
+        assert e.op.rule == TableRule("rowwise", EPS, None)
     # parameters in builder order: bottom linears, tables, top linears
     ps = _params(m)
     dense_ps = [p.clone().requires_grad_(True) for p in ps[:2 * nb] + ps[2 * nb + T:]]
@@ -209,20 +210,24 @@ def test_column_split_and_dense_replicas_are_rejected(monkeypatch):
     m = _table_model(lambda m: RowwiseAdagradOptimizer(m, 0.05))
     ex = m.init_layers()
     op = m.layers[0]
-    whole = ParallelConfig([1, 1], [0])
-    ex._check_rowwise_table(op, whole, op.weight_layouts(whole)[0])
-    rows2 = ParallelConfig([1, 1, 2], [0, 1])
-    ex._check_rowwise_table(op, rows2, op.weight_layouts(rows2)[0])
+
+    def check(pc):          # as Executor._build_weights does: the rule function, a reason raises
+        lay = op.weight_layouts(pc)[0]
+        rule, why = op.shard_rule(ex.optimizer, pc, lay, 0, lay.holders[0], sparse_dp=E.SPARSE_DP)
+        if why:
+            raise NotImplementedError(f"{op.name}: {why}")
+        return rule
+    assert check(ParallelConfig([1, 1], [0])) == TableRule("rowwise", EPS, None)
+    assert check(ParallelConfig([1, 1, 2], [0, 1])) == TableRule("rowwise", EPS, None)
     cols2 = ParallelConfig([2, 1], [0, 1])
     with pytest.raises(NotImplementedError, match="mytable.*column-split"):
-        ex._check_rowwise_table(op, cols2, op.weight_layouts(cols2)[0])
+        check(cols2)
     dp2 = ParallelConfig([1, 2], [0, 1])
-    lay = op.weight_layouts(dp2)[0]
-    assert lay.replication() == 2
-    ex._check_rowwise_table(op, dp2, lay)
+    assert op.weight_layouts(dp2)[0].replication() == 2
+    assert check(dp2) == TableRule("rowwise", EPS, (0, 1))
     monkeypatch.setattr(E, "SPARSE_DP", False)
     with pytest.raises(NotImplementedError, match="mytable.*FLEXMI_SPARSE_DP"):
-        ex._check_rowwise_table(op, dp2, lay)
+        check(dp2)
 
 
 # ------------------------------------------------------------------ search and command line
@@ -242,8 +247,11 @@ def test_search_pricing():
     assert isinstance(m.optimizer, RowwiseAdagradOptimizer)
     g = SimGraph(m, 2)
     gs = SimGraph(cli._model("dlrm-tiny", 2, 64, True, "sgd"), 2)
-    assert g.sparse_ok and g.sparse_dp_ok and g.sdp_always
     from flexmi.ops.embedding import Embedding
+    # sparse whether replicated or not, whatever the byte comparison says (4 rows: dense under SGD)
+    assert Embedding.table_rule(m.optimizer, 4, 16, 32, (0,)) == (TableRule("rowwise", 1e-10, None), None)
+    assert Embedding.table_rule(m.optimizer, 4, 16, 32, (0, 1)) == (TableRule("rowwise", 1e-10, (0, 1)), None)
+    assert not Embedding.sdp_prefer_sparse(4, 16, 32, 2)
     n = dense_under_sgd = 0
     for k, op in enumerate(g.ops):
         if op.op_type != OperatorType.OP_EMBEDDING:

@@ -66,6 +66,7 @@ def _steps(m, d, s, first, n):
 
 def _check_entries(m, world):
     from flexmi.core.types import OperatorType
+    from flexmi.ops.embedding import TableRule
     ex = m._ex()
     embs = [e for e in ex.wentries.values() if e.op.op_type == OperatorType.OP_EMBEDDING]
     assert len(embs) == 4
@@ -73,13 +74,13 @@ def _check_entries(m, world):
     for e in embs:
         if e.box is None:                  # this rank holds no shard of the table
             continue
-        assert e.op.sparse_rowwise == 1e-10 and e.op.sparse_adagrad is None and not e.op.sparse_sgd
+        assert e.op.rule.kind == "rowwise" and e.op.rule.eps == 1e-10 and not e.op.rule.host
         assert e.sparse and e.grad is None and e.group is None and id(e) not in in_groups
         assert set(e.state) == {"h"} and tuple(e.state["h"].shape) == (e.shape[0], 1)
         if e.layout.replication() == 1:
-            assert e.op.sparse_dp is None
+            assert e.op.rule == TableRule("rowwise", 1e-10, None)
         else:
-            assert e.op.sparse_dp == tuple(range(world))
+            assert e.op.rule == TableRule("rowwise", 1e-10, tuple(range(world)))
     return sum(e.layout.replication() > 1 for e in embs)
 
 
