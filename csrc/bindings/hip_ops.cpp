@@ -191,6 +191,24 @@ void check_cuda(const torch::Tensor& t, const char* name) {
 
 int is_bf16(const torch::Tensor& t) { return t.scalar_type() == torch::kBFloat16 ? 1 : 0; }
 
+// The arguments of a dense optimizer launch (sgd / sgd_segs / adam / adagrad): contiguous fp32 W
+// and G of one size on one GPU, every state given likewise, an optional contiguous bf16 mirror
+// of W's numel, and the step size as an fp32 scalar on that GPU
+void check_update(const char* op, const torch::Tensor& W, const torch::Tensor& G,
+                  std::initializer_list<c10::optional<torch::Tensor>> states, const c10::optional<torch::Tensor>& Wc,
+                  const torch::Tensor& step) {
+  auto like_w = [&](const torch::Tensor& t, torch::ScalarType dt) {
+    return t.scalar_type() == dt && t.is_contiguous() && t.numel() == W.numel() && t.device() == W.device();
+  };
+  TORCH_CHECK(W.is_cuda() && like_w(W, torch::kFloat32) && like_w(G, torch::kFloat32), op,
+              ": W and G must be contiguous fp32 tensors of one size on one GPU");
+  for (const auto& s : states)
+    TORCH_CHECK(!s.has_value() || !s->defined() || like_w(*s, torch::kFloat32), op, ": contiguous fp32 state of W's size");
+  TORCH_CHECK(!Wc.has_value() || !Wc->defined() || like_w(*Wc, torch::kBFloat16), op, ": contiguous bf16 mirror of W's size");
+  TORCH_CHECK(step.scalar_type() == torch::kFloat32 && step.numel() >= 1 && step.device() == W.device(), op,
+              ": the step size must be an fp32 scalar on W's GPU");
+}
+
 // ----------------------------------------------------------------------------- GEMM
 int gemm(torch::Tensor A, int64_t lda, int64_t sA, bool a_kcontig, torch::Tensor B, int64_t ldb, int64_t sB, bool b_kcontig,
          torch::Tensor C, int64_t ldc, int64_t sC, c10::optional<torch::Tensor> bias, int64_t M, int64_t N, int64_t K,
@@ -256,11 +274,8 @@ void sgd_segs(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, 
               torch::Tensor lr, std::vector<int64_t> off, std::vector<int64_t> len, double wd, double mom, bool nesterov,
               bool zero_g) {
   TORCH_CHECK(off.size() == len.size(), "sgd_segs: off/len");
-  TORCH_CHECK(W.is_cuda() && W.scalar_type() == torch::kFloat32 && W.is_contiguous() && G.scalar_type() == torch::kFloat32 &&
-                  G.is_contiguous() && G.numel() == W.numel(), "sgd_segs: fp32 W / G");
-  TORCH_CHECK(mom <= 0.0 || (V.has_value() && V->defined() && V->numel() == W.numel()), "sgd_segs: momentum buffer");
-  if (Wc.has_value() && Wc->defined())
-    TORCH_CHECK(Wc->scalar_type() == torch::kBFloat16 && Wc->numel() == W.numel(), "sgd_segs: bf16 mirror");
+  check_update("sgd_segs", W, G, {V}, Wc, lr);
+  TORCH_CHECK(mom <= 0.0 || (V.has_value() && V->defined()), "sgd_segs: momentum buffer");
   for (size_t i = 0; i < off.size(); ++i)
     TORCH_CHECK(off[i] >= 0 && len[i] >= 0 && off[i] + len[i] <= W.numel(), "sgd_segs: range outside the buffer");
   // the kernel's vector body assumes the flat buffers start 16-B aligned (8-B for the bf16 mirror)
@@ -819,23 +834,22 @@ void dot_bwd(std::vector<torch::Tensor> zs, int64_t ldz, torch::Tensor dout, int
 
 void sgd(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, c10::optional<torch::Tensor> Wc, torch::Tensor lr,
          double wd, double mom, bool nesterov, bool zero_grad) {
-  TORCH_CHECK(W.numel() == G.numel(), "sgd: size mismatch");
+  check_update("sgd", W, G, {V}, Wc, lr);
+  TORCH_CHECK(mom <= 0.0 || (V.has_value() && V->defined()), "sgd: momentum buffer");
   fm_sgd_update(W.data_ptr<float>(), G.data_ptr<float>(), (float*)mptr(V), (unsigned short*)mptr(Wc), lr.data_ptr<float>(),
                 W.numel(), (float)wd, (float)mom, nesterov ? 1 : 0, zero_grad ? 1 : 0, cur());
 }
 
 void adam(torch::Tensor W, torch::Tensor G, torch::Tensor M, torch::Tensor V, c10::optional<torch::Tensor> Wc,
           torch::Tensor alpha_t, double b1, double b2, double wd, double eps, bool zero_grad) {
-  TORCH_CHECK(alpha_t.scalar_type() == torch::kFloat32 && alpha_t.is_cuda(), "alpha_t: fp32 device scalar");
+  check_update("adam", W, G, {M, V}, Wc, alpha_t);
   fm_adam_update(W.data_ptr<float>(), G.data_ptr<float>(), M.data_ptr<float>(), V.data_ptr<float>(), (unsigned short*)mptr(Wc),
                  W.numel(), alpha_t.data_ptr<float>(), (float)b1, (float)b2, (float)wd, (float)eps, zero_grad ? 1 : 0, cur());
 }
 
 void adagrad(torch::Tensor W, torch::Tensor G, torch::Tensor H, c10::optional<torch::Tensor> Wc, torch::Tensor lr, double wd,
              double eps, bool zero_grad) {
-  TORCH_CHECK(W.numel() == G.numel() && W.numel() == H.numel(), "adagrad: size mismatch");
-  TORCH_CHECK(lr.scalar_type() == torch::kFloat32 && lr.is_cuda(), "lr: fp32 device scalar");
-  TORCH_CHECK(!Wc.has_value() || !Wc->defined() || Wc->numel() == W.numel(), "adagrad: mirror size mismatch");
+  check_update("adagrad", W, G, {H}, Wc, lr);
   fm_adagrad_update(W.data_ptr<float>(), G.data_ptr<float>(), H.data_ptr<float>(), (unsigned short*)mptr(Wc),
                     lr.data_ptr<float>(), W.numel(), (float)wd, (float)eps, zero_grad ? 1 : 0, cur());
 }

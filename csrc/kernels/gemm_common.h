@@ -3,7 +3,7 @@
 // fused epilogue (alpha, bias, activation, fused activation-backward of the layer below, beta
 // accumulate, bf16/fp32 output, split-K slabs).
 #pragma once
-#include "common.h"
+#include "update_rule.h"
 
 namespace {
 
@@ -79,7 +79,7 @@ struct GemmP {
   int n_fast;   // tile order: column tiles fastest (A row-block reused by consecutive tiles on one XCD)
   // fused SGD (dW GEMMs whose gradient has no other consumer): instead of storing the gradient,
   // the epilogue updates the fp32 master W (same [M][ldc] layout as C), its momentum and bf16 mirror
-  // exactly as fm_sgd_kernel would (optim.hip) -- the gradient never round-trips through HBM
+  // by the rule of update_rule.h -- the gradient never round-trips through HBM
   float* uw;             // nullptr = plain GEMM
   unsigned short* uwc;   // bf16 compute mirror (nullptr: none)
   float* uv;             // momentum buffer (used when umom > 0)
@@ -90,42 +90,17 @@ struct GemmP {
   int dma;   // operands staged by LDS-DMA (gemm.hip: full tiles, no row sums)
 };
 
-// W -= lr * (g + wd W) (momentum / Nesterov as fm_sgd_kernel), one element at offset o of W
-// (P = GemmP or gemm_f32.hip's GemmF: the same uw / uwc / uv / ulr / uwd / umom / unest fields)
+// The SGD step on W at offset o with gradient g, by update_rule.h's rule (P = GemmP or
+// gemm_f32_common.h's GemmF: the same uw / uwc / uv / ulr / uwd / umom / unest fields)
 template <class P>
 FM_DEVICE void sgd_apply1(const P& p, long o, float g) {
-  const float lr = p.ulr[0];
-  float w = p.uw[o];
-  g += p.uwd * w;
-  if (p.umom > 0.f) {
-    const float v = p.uv[o] * p.umom + g;
-    p.uv[o] = v;
-    g = p.unest ? g + p.umom * v : v;
-  }
-  w -= lr * g;
-  p.uw[o] = w;
-  if (p.uwc) p.uwc[o] = f2bf(w);
+  update_lanes(SgdRule{p.uwd, p.umom, p.unest}, UpdBufs<SgdRule>{p.uw, {p.uv}, p.uwc}, p.ulr[0], o, g);
 }
 
 // four consecutive elements at a 16-B aligned offset o
 template <class P>
 FM_DEVICE void sgd_apply4(const P& p, long o, f32x4_t g) {
-  const float lr = p.ulr[0];
-  f32x4_t w = *reinterpret_cast<const f32x4_t*>(p.uw + o);
-  g += p.uwd * w;
-  if (p.umom > 0.f) {
-    const f32x4_t v = *reinterpret_cast<const f32x4_t*>(p.uv + o) * p.umom + g;
-    *reinterpret_cast<f32x4_t*>(p.uv + o) = v;
-    g = p.unest ? g + p.umom * v : v;
-  }
-  w -= lr * g;
-  *reinterpret_cast<f32x4_t*>(p.uw + o) = w;
-  if (p.uwc) {
-    bf16x4_t c;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) c[r] = (short)f2bf(w[r]);
-    *reinterpret_cast<bf16x4_t*>(p.uwc + o) = c;
-  }
+  update_lanes(SgdRule{p.uwd, p.umom, p.unest}, UpdBufs<SgdRule>{p.uw, {p.uv}, p.uwc}, p.ulr[0], o, g);
 }
 
 // tile coordinates of remapped block id: consecutive ids share an XCD (xcd_remap), so the

@@ -16,7 +16,7 @@
 //             gradient of the weight is never stored).
 // The first version kept x in global memory and looped rows one load at a time: latency-bound at
 // 1 wave per SIMD (dW 20 + 12 us on the MLPerf step, gpurun_out r5e); measured again in r5f.
-#include "common.h"
+#include "update_rule.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -190,7 +190,7 @@ __global__ void __launch_bounds__(SK_DW_NT) fm_smallk_dw_part(const T* __restric
 
 // dW / db from the P partials in a fixed order (deterministic): block = 64 outputs x 4 slices of
 // the partials, the slices combined through LDS; dw[n][k] += sum, db[n] += sum; with lr != null
-// the SGD step of optim.hip fm_sgd_kernel is applied to W = dw instead (the gradient is never
+// the SGD step of update_rule.h is applied to W = dw instead (the gradient is never
 // stored; momentum V and the bf16 mirror Wc optional)
 __global__ void __launch_bounds__(256) fm_smallk_dw_reduce(const float* __restrict__ ws, int P, int K, int N,
                                                           float* __restrict__ dw, float* __restrict__ db,
@@ -226,15 +226,7 @@ __global__ void __launch_bounds__(256) fm_smallk_dw_reduce(const float* __restri
     dw[i] += sum;
     return;
   }
-  float gi = sum + wd * dw[i];
-  if (mom > 0.f) {
-    const float vi = V[i] * mom + gi;
-    V[i] = vi;
-    gi = nesterov ? gi + mom * vi : vi;
-  }
-  const float wi = dw[i] - lr_p[0] * gi;
-  dw[i] = wi;
-  if (Wc) Wc[i] = f2bf(wi);
+  update_lanes(SgdRule{wd, mom, nesterov}, UpdBufs<SgdRule>{dw, {V}, Wc}, lr_p[0], i, sum);
 }
 
 }  // namespace

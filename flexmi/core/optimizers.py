@@ -4,7 +4,10 @@ Reference: one single-point Legion task per parameter gathers every gradient rep
 sums them and applies the update (``optimizer_kernel.cu:44-110``).  flexmi: gradients are
 reduced by RCCL all-reduce (bucketed, overlapped with backward), then ONE multi-tensor kernel
 updates every parameter shard of the rank in a single pass over flat fp32 buffers and
-refreshes the bf16 compute copies in the same pass (``csrc/kernels/optim.hip``).
+refreshes the bf16 compute copies in the same pass (``csrc/kernels/optim.hip``).  On the device
+each rule's arithmetic is written once (``csrc/kernels/update_rule.h``) and shared by the
+optimizer launches and the dW GEMMs that fuse the SGD step; here each optimizer holds its rule
+as ``update_torch`` and its launch as ``update_hip``, and the executor calls ``update``.
 Update rules are bit-for-bit the reference's:
 
   SGD : g = ∇ + wd·W; V = μV + g; g = nesterov ? g + μV : V (only if μ>0); W -= lr·g
@@ -75,6 +78,28 @@ class Optimizer:
     # replicated tables trained by touched-row exchange (Embedding.sdp_*): an SGD form only
     sparse_dp_capable = False
 
+    # ---- the dense update.  A rule answers two things: update_torch(w, g, state, step=None), the
+    # update as torch arithmetic, and update_hip(w, g, state, comp, step, zero_grad), its HIP launch
+    # (bf16 mirror ``comp`` or None; zero_grad: the kernel leaves the consumed gradient zeroed).
+    # ``step`` is the device scalar the executor steps with; without one update_torch uses the
+    # host value.
+    def device_step(self, ex):
+        """The device scalar of executor ``ex`` this rule steps with."""
+        return ex.lr_tensor
+
+    def advance_device(self, counters):
+        """Advance the executor's device-side step counters (only Adam keeps any)."""
+
+    def update(self, ex, w, g, state, comp, zero_grad):
+        """One step of executor ``ex`` over flat fp32 master ``w``, gradient ``g`` and ``state``."""
+        step = self.device_step(ex)
+        if ex.backend == "hip":
+            self.update_hip(w, g, state, comp, step, zero_grad)
+        else:
+            self.update_torch(w, g, state, step)
+            if comp is not None:
+                comp.copy_(w)
+
     def state_dict(self):
         return {}
 
@@ -108,13 +133,27 @@ class SGDOptimizer(Optimizer):
     def sparse_dp_capable(self):
         return self.sparse_capable
 
-    def update_torch(self, w, g, state):
+    def update_torch(self, w, g, state, step=None):
         gt = g + self.weight_decay * w
         if self.momentum > 0:
             v = state["v"]
             v.mul_(self.momentum).add_(gt)
             gt = gt + self.momentum * v if self.nesterov else v
-        w.sub_(self.lr * gt)
+        w.sub_((self.lr if step is None else step) * gt)
+
+    @property
+    def constants(self):
+        """(weight decay, momentum, nesterov): the rule's constants as every SGD launch takes them."""
+        return self.weight_decay, self.momentum, self.nesterov
+
+    def update_hip(self, w, g, state, comp, step, zero_grad, segs=None):
+        """segs: update only these (offset, length) ranges of the flat buffers, in one launch."""
+        from flexmi.ops import _kernels as K
+        v = state.get("v") if self.momentum > 0 else None
+        if segs is None:
+            K.sgd_update(w, g, v, comp, step, *self.constants, zero_grad=zero_grad)
+        else:
+            K.C().sgd_segs(w, g, v, comp, step, [s[0] for s in segs], [s[1] for s in segs], *self.constants, zero_grad)
 
     def state_dict(self):
         return {"lr": self.lr}
@@ -153,12 +192,27 @@ class AdamOptimizer(Optimizer):
     def state_names(self):
         return ["m", "v"]
 
-    def update_torch(self, w, g, state):
+    def device_step(self, ex):
+        return ex.adam_state[2:3]
+
+    def advance_device(self, counters):
+        """``next()`` on the executor's device-side ``[β1ᵗ, β2ᵗ, α_t]``: three in-place tensor ops,
+        so the step stays graph-capturable."""
+        counters[0:1].mul_(self.beta1)
+        counters[1:2].mul_(self.beta2)
+        counters[2:3].copy_(self.alpha * torch.sqrt(1 - counters[1:2]) / (1 - counters[0:1]))
+
+    def update_torch(self, w, g, state, step=None):
         gt = g + self.weight_decay * w
         m, v = state["m"], state["v"]
         m.mul_(self.beta1).add_((1 - self.beta1) * gt)
         v.mul_(self.beta2).add_((1 - self.beta2) * gt * gt)
-        w.sub_(self.alpha_t * m / (v.sqrt() + self.epsilon))
+        w.sub_((self.alpha_t if step is None else step) * m / (v.sqrt() + self.epsilon))
+
+    def update_hip(self, w, g, state, comp, step, zero_grad):
+        from flexmi.ops import _kernels as K
+        K.adam_update(w, g, state["m"], state["v"], comp, step, self.beta1, self.beta2, self.weight_decay, self.epsilon,
+                      zero_grad=zero_grad)
 
     def state_dict(self):
         return {"alpha": self.alpha, "beta1_t": self.beta1_t, "beta2_t": self.beta2_t, "alpha_t": self.alpha_t}
@@ -199,11 +253,15 @@ class AdagradOptimizer(Optimizer):
     # replicated tables stay dense: the replica all-reduce sums the gradients before they are squared
     sparse_dp_capable = False
 
-    def update_torch(self, w, g, state):
+    def update_torch(self, w, g, state, step=None):
         gt = g + self.weight_decay * w
         h = state["h"]
         h.addcmul_(gt, gt)
-        w.sub_(self.lr * gt / (h.sqrt() + self.epsilon))
+        w.sub_((self.lr if step is None else step) * gt / (h.sqrt() + self.epsilon))
+
+    def update_hip(self, w, g, state, comp, step, zero_grad):
+        from flexmi.ops import _kernels as K
+        K.adagrad_update(w, g, state["h"], comp, step, self.weight_decay, self.epsilon, zero_grad=zero_grad)
 
     def state_dict(self):
         return {"lr": self.lr}

@@ -28,7 +28,7 @@ import torch
 
 from flexmi.core.loss_metrics import NUM_SLOTS, PerfMetrics, loss_and_metrics_torch
 from flexmi.core.initializers import _native_cpu
-from flexmi.core.optimizers import AdagradOptimizer, AdamOptimizer, SGDOptimizer
+from flexmi.core.optimizers import SGDOptimizer
 from flexmi.core.types import DataType, LossType, to_torch_dtype
 from flexmi.ops.base import OpCtx
 from flexmi.parallel.layout import Layout, ParallelConfig, ReshardPlan, box_intersect, box_volume
@@ -1658,8 +1658,7 @@ class Executor:
             if n_out == 1 or K._dw_lib(rows, n_out, n_in, self.cdtype):
                 continue
             c.fused_sgd = K.FusedSGD(e.master, e.compute if g.compute is not g.master else None,
-                                     e.state.get("v") if opt.momentum > 0 else None, self.lr_tensor,
-                                     opt.weight_decay, opt.momentum, opt.nesterov)
+                                     e.state.get("v") if opt.momentum > 0 else None, self.lr_tensor, *opt.constants)
             c.fused_sgd_state = self.fused_sgd_state
             self.fused_sgd_entries.append(e)
         if not self.fused_sgd_entries:
@@ -2153,14 +2152,8 @@ class Executor:
     def _optimizer_step(self, fused=False):
         """fused: the weights in ``fused_sgd_entries`` were already updated inside their dW GEMMs
         (_plan_fused_sgd); only the remaining ranges of each group are updated here."""
-        from flexmi.ops import _kernels as K
         opt = self.optimizer
-        if isinstance(opt, AdamOptimizer):
-            # device-side bias-correction counters (capturable): [beta1^t, beta2^t, alpha_t]
-            st = self.adam_state
-            st[0:1].mul_(opt.beta1)
-            st[1:2].mul_(opt.beta2)
-            st[2:3].copy_(opt.alpha * torch.sqrt(1 - st[1:2]) / (1 - st[0:1]))
+        opt.advance_device(self.adam_state)
         for g in self.groups:
             if g.numel == 0:
                 continue
@@ -2169,77 +2162,18 @@ class Executor:
                 continue
             comp = g.compute if g.compute is not g.master else None
             rest = getattr(g, "sgd_rest", None) if fused else None
-            if rest is not None:
+            if rest is not None:     # only SGD plans fused weights (_plan_fused_sgd)
                 if rest:
-                    K.C().sgd_segs(g.master, g.gradbuf, g.state.get("v") if opt.momentum > 0 else None, comp,
-                                   self.lr_tensor, [r[0] for r in rest], [r[1] for r in rest], opt.weight_decay,
-                                   opt.momentum, opt.nesterov, True)
+                    opt.update_hip(g.master, g.gradbuf, g.state, comp, self.lr_tensor, True, segs=rest)
                 continue
-            if self.backend == "hip":
-                # the kernels consume the gradient and leave it zeroed for the next backward
-                if isinstance(opt, SGDOptimizer):
-                    K.sgd_update(g.master, g.gradbuf, g.state.get("v"), comp, self.lr_tensor, opt.weight_decay,
-                                 opt.momentum, opt.nesterov, zero_grad=True)
-                elif isinstance(opt, AdagradOptimizer):
-                    K.adagrad_update(g.master, g.gradbuf, g.state["h"], comp, self.lr_tensor, opt.weight_decay,
-                                     opt.epsilon, zero_grad=True)
-                else:
-                    K.adam_update(g.master, g.gradbuf, g.state["m"], g.state["v"], comp, self.adam_state[2:3],
-                                  opt.beta1, opt.beta2, opt.weight_decay, opt.epsilon, zero_grad=True)
-            else:
-                if isinstance(opt, SGDOptimizer):
-                    gt = g.gradbuf + opt.weight_decay * g.master
-                    if opt.momentum > 0:
-                        v = g.state["v"]
-                        v.mul_(opt.momentum).add_(gt)
-                        gt = gt + opt.momentum * v if opt.nesterov else v
-                    g.master.sub_(self.lr_tensor * gt)
-                elif isinstance(opt, AdagradOptimizer):
-                    gt = g.gradbuf + opt.weight_decay * g.master
-                    h_ = g.state["h"]
-                    h_.addcmul_(gt, gt)
-                    g.master.sub_(self.lr_tensor * gt / (h_.sqrt() + opt.epsilon))
-                else:
-                    gt = g.gradbuf + opt.weight_decay * g.master
-                    m_, v_ = g.state["m"], g.state["v"]
-                    m_.mul_(opt.beta1).add_((1 - opt.beta1) * gt)
-                    v_.mul_(opt.beta2).add_((1 - opt.beta2) * gt * gt)
-                    g.master.sub_(self.adam_state[2] * m_ / (v_.sqrt() + opt.epsilon))
-                if comp is not None:
-                    comp.copy_(g.master)
+            # the HIP kernels consume the gradient and leave it zeroed for the next backward
+            opt.update(self, g.master, g.gradbuf, g.state, comp, zero_grad=True)
 
     def _zero_opt_step(self, g, opt):
         """The optimizer on this rank's shard: fp32 master shard, reduce-scattered gradient shard
         and the sharded state, one fused kernel launch over the whole shard buffer (the slices of
         all buckets are packed back to back)."""
-        from flexmi.ops import _kernels as K
-        m, gr, st = g.mshard, g.gshard, g.state
-        if self.backend == "hip":
-            if isinstance(opt, SGDOptimizer):
-                K.sgd_update(m, gr, st.get("v"), None, self.lr_tensor, opt.weight_decay, opt.momentum, opt.nesterov)
-            elif isinstance(opt, AdagradOptimizer):
-                K.adagrad_update(m, gr, st["h"], None, self.lr_tensor, opt.weight_decay, opt.epsilon)
-            else:
-                K.adam_update(m, gr, st["m"], st["v"], None, self.adam_state[2:3], opt.beta1, opt.beta2,
-                              opt.weight_decay, opt.epsilon)
-        elif isinstance(opt, SGDOptimizer):
-            gt = gr + opt.weight_decay * m
-            if opt.momentum > 0:
-                v = st["v"]
-                v.mul_(opt.momentum).add_(gt)
-                gt = gt + opt.momentum * v if opt.nesterov else v
-            m.sub_(self.lr_tensor * gt)
-        elif isinstance(opt, AdagradOptimizer):
-            gt = gr + opt.weight_decay * m
-            h_ = st["h"]
-            h_.addcmul_(gt, gt)
-            m.sub_(self.lr_tensor * gt / (h_.sqrt() + opt.epsilon))
-        else:
-            gt = gr + opt.weight_decay * m
-            m_, v_ = st["m"], st["v"]
-            m_.mul_(opt.beta1).add_((1 - opt.beta1) * gt)
-            v_.mul_(opt.beta2).add_((1 - opt.beta2) * gt * gt)
-            m.sub_(self.adam_state[2] * m_ / (v_.sqrt() + opt.epsilon))
+        opt.update(self, g.mshard, g.gshard, g.state, None, zero_grad=False)
 
     # ------------------------------------------------------------------ loss
     def _loss_kernel(self, compute_grad):
