@@ -18,6 +18,12 @@ criteo_kaggle, summit, summit_large, kaggle_day1, tiny) seeds the architecture f
 accumulator per table element and updates non-replicated tables sparsely; row-wise Adagrad keeps
 one per table ROW and trains every table sparsely, replicated ones included
 (``flexmi/core/optimizers.py``).
+``--auc`` (flexmi extension) adds the streaming ROC AUC to the training metrics and to the final
+stderr line.  ``--eval-dataset FILE.h5`` (implies ``--auc``) runs a held-out pass over the file's
+whole batches after every epoch (``--eval-data-size N`` caps it) and prints ``EVAL epoch E: loss ...
+accuracy ... auc ... (+-bound)``; ``--auc-threshold A`` stops after the first epoch whose
+evaluation AUC is >= A (the MLPerf stopping rule).  ``main()`` returns ``(samples/s, metrics)``;
+``metrics.eval`` is the last evaluation's ``PerfMetrics`` (None without ``--eval-dataset``).
 """
 from __future__ import annotations
 
@@ -50,6 +56,24 @@ def main(argv=None):
         del argv[k:k + 2]
         if optname not in ("sgd", "adagrad", "rowwise_adagrad"):
             raise SystemExit(f"--optimizer {optname}: expected sgd, adagrad or rowwise_adagrad")
+    want_auc = "--auc" in argv
+    if want_auc:
+        argv.remove("--auc")
+    eval_path, eval_size, auc_threshold = None, 0, None
+    for flag in ("--eval-dataset", "--eval-data-size", "--auc-threshold"):
+        if flag in argv:
+            k = argv.index(flag)
+            v = argv[k + 1]
+            del argv[k:k + 2]
+            if flag == "--eval-dataset":
+                eval_path = v
+            elif flag == "--eval-data-size":
+                eval_size = int(v)
+            else:
+                auc_threshold = float(v)
+    if auc_threshold is not None and not eval_path:
+        raise SystemExit("--auc-threshold needs --eval-dataset: the threshold is on the evaluation AUC")
+    want_auc = want_auc or bool(eval_path)
     dcfg = DLRMConfig.parse_args(["dlrm"] + argv, base)
     cfg = FFConfig()
     cfg.parse_args(["dlrm"] + argv)
@@ -63,8 +87,33 @@ def main(argv=None):
     opt = {"sgd": SGDOptimizer, "adagrad": AdagradOptimizer,
            "rowwise_adagrad": RowwiseAdagradOptimizer}[optname](model, cfg.learningRate)
     model.compile(opt, loss,
-                  [MetricsType.METRICS_ACCURACY, MetricsType.METRICS_MEAN_SQUARED_ERROR])
+                  [MetricsType.METRICS_ACCURACY, MetricsType.METRICS_MEAN_SQUARED_ERROR] +
+                  ([MetricsType.METRICS_AUC] if want_auc else []))
     ex = model.init_layers()
+    edata = None
+    if eval_path:
+        import copy
+        ecfg = copy.copy(dcfg)
+        ecfg.data_size = eval_size
+        edata = HDF5DLRMData(model, dense_in, sparse, ecfg, path=eval_path)
+
+    def evaluate(epoch):
+        """Held-out pass over the whole batches of --eval-dataset: forward + metrics only."""
+        ex.training = False
+        model.reset_metrics()
+        edata.loader.reset()
+        for _ in range(edata.nb):
+            edata.next_batch()
+            model.forward()
+            model.compute_metrics()
+        em = model.get_perf_metrics()
+        if comm.rank == 0:
+            print(f"EVAL epoch {epoch}: loss {em.get_loss():.5f} accuracy {em.get_accuracy():.2f}% "
+                  f"auc {em.get_auc():.5f} (+-{em.get_auc_bound():.1e})", flush=True)
+        ex.training = True
+        model.reset_metrics()
+        return em
+
     if dcfg.dataset_path:
         data = HDF5DLRMData(model, dense_in, sparse, dcfg)
         num_samples = data.num_samples
@@ -81,6 +130,9 @@ def main(argv=None):
     sync()
     comm.barrier()
     t0 = time.perf_counter()
+    m = em = None
+    t_eval = 0.0
+    epochs_done = 0
     for epoch in range(cfg.epochs):
         model.reset_metrics()
         for it in range(iters):
@@ -93,18 +145,35 @@ def main(argv=None):
             model.update()
             if epoch > 0 or it > 0:
                 model.end_trace(111)
+        epochs_done = epoch + 1
+        if edata is not None:
+            # the evaluation pass resets the metrics: keep this epoch's training metrics, and keep
+            # the pass out of the training time
+            sync()
+            te = time.perf_counter()
+            m = model.get_perf_metrics()
+            em = evaluate(epoch)
+            sync()
+            t_eval += time.perf_counter() - te
+            if auc_threshold is not None and em.get_auc() >= auc_threshold:
+                break               # MLPerf stopping rule: first epoch that reaches the target
     sync()
     comm.barrier()
-    el = time.perf_counter() - t0
-    m = model.get_perf_metrics()
-    samples = num_samples * cfg.epochs
+    el = time.perf_counter() - t0 - t_eval
+    if m is None:
+        m = model.get_perf_metrics()
+    m.eval = em                     # last evaluation PerfMetrics, None without --eval-dataset
+    samples = num_samples * epochs_done
     if comm.rank == 0:
-        print(f"[dlrm {dcfg.name}] {cfg.epochs} epoch(s) x {iters} iterations, batch {cfg.batchSize}, "
+        auc_s = f" auc {m.get_auc():.5f} (+-{m.get_auc_bound():.1e})" if want_auc else ""
+        print(f"[dlrm {dcfg.name}] {epochs_done} epoch(s) x {iters} iterations, batch {cfg.batchSize}, "
               f"{comm.world} device(s), {'dataset ' + dcfg.dataset_path if dcfg.dataset_path else 'random data'}: "
-              f"loss {m.get_loss():.5f} accuracy {m.get_accuracy():.2f}%", file=sys.stderr)
+              f"loss {m.get_loss():.5f} accuracy {m.get_accuracy():.2f}%{auc_s}", file=sys.stderr)
         print(f"ELAPSED TIME = {el:.4f}s, THROUGHPUT = {samples / el:.2f} samples/s", flush=True)
     if hasattr(data, "close"):
         data.close()
+    if edata is not None:
+        edata.close()
     return samples / el, m
 
 

@@ -95,6 +95,8 @@ void fm_adam_update(float* W, float* G, float* M, float* V, unsigned short* Wc, 
 void fm_cast_bf16(const float* src, unsigned short* dst, long n, hipStream_t s);
 void fm_loss_fwd_bwd(const void* logits, int logits_bf16, const void* labels, void* grad, int grad_bf16, long B, int C,
                      int loss_type, float scale, float* acc, int mask, float clamp_t, hipStream_t s);
+void fm_auc_hist_variant(const void* scores, int scores_bf16, const float* labels, long B, long long* hist, long long* invalid,
+                         int shift, int rounds, hipStream_t s);
 void fm_unary_forward(int code, const void* x, void* y, long n, int bf16, hipStream_t s);
 void fm_unary_backward(int code, const void* x, const void* y, const void* dy, void* dx, long n, int acc, int bf16,
                        hipStream_t s);
@@ -865,6 +867,24 @@ void loss(int64_t loss_type, torch::Tensor logits, torch::Tensor labels, c10::op
                   acc.data_ptr<float>(), (int)mask, (float)clamp_t, cur());
 }
 
+// METRICS_AUC: hist[label >= 0.5][key(score) >> shift] += 1 (int64 [2, 1 << (32 - shift)]), NaN scores into
+// invalid; rounds: lone-key peel rounds per wave before plain atomics (< 0: the kernel's default; tools/bench_auc.py)
+void auc_hist(torch::Tensor scores, torch::Tensor labels, torch::Tensor hist, torch::Tensor invalid, int64_t shift,
+              int64_t rounds) {
+  TORCH_CHECK(shift >= 1 && shift <= 31, "auc_hist: shift ", shift, " outside [1, 31]");
+  TORCH_CHECK(scores.is_cuda() && scores.is_contiguous() &&
+                  (scores.scalar_type() == torch::kFloat32 || scores.scalar_type() == torch::kBFloat16),
+              "auc_hist: contiguous fp32 or bf16 device scores");
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() && labels.scalar_type() == torch::kFloat32 &&
+                  labels.numel() == scores.numel(), "auc_hist: one contiguous fp32 label per score");
+  TORCH_CHECK(hist.is_cuda() && hist.is_contiguous() && hist.scalar_type() == torch::kInt64 &&
+                  hist.numel() == (int64_t)2 << (32 - shift), "auc_hist: hist must be int64 [2, 1 << (32 - shift)]");
+  TORCH_CHECK(invalid.is_cuda() && invalid.scalar_type() == torch::kInt64 && invalid.numel() == 1, "auc_hist: invalid");
+  fm_auc_hist_variant(scores.data_ptr(), is_bf16(scores), labels.data_ptr<float>(), scores.numel(),
+                      (long long*)hist.data_ptr<int64_t>(), (long long*)invalid.data_ptr<int64_t>(), (int)shift,
+                      (int)std::max<int64_t>(-1, std::min<int64_t>(rounds, 64)), cur());
+}
+
 void unary_fwd(int64_t code, torch::Tensor x, torch::Tensor y) { fm_unary_forward((int)code, x.data_ptr(), y.data_ptr(), x.numel(), is_bf16(x), cur()); }
 void unary_bwd(int64_t code, torch::Tensor x, torch::Tensor y, torch::Tensor dy, torch::Tensor dx, bool acc) {
   fm_unary_backward((int)code, x.data_ptr(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), acc, is_bf16(x), cur());
@@ -1492,6 +1512,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("cast_bf16", &cast_bf16);
   m.def("loss", &loss, py::arg("loss_type"), py::arg("logits"), py::arg("labels"), py::arg("grad"), py::arg("scale"),
         py::arg("acc"), py::arg("mask"), py::arg("clamp_t") = 0.0);
+  m.def("auc_hist", &auc_hist, py::arg("scores"), py::arg("labels"), py::arg("hist"), py::arg("invalid"), py::arg("shift"),
+        py::arg("rounds") = -1);
   m.def("unary_fwd", &unary_fwd);
   m.def("unary_bwd", &unary_bwd);
   m.def("binary_fwd", &binary_fwd);

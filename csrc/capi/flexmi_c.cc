@@ -923,6 +923,8 @@ static float pm_float(flexmi_perf_metrics_t pm, const char* meth) {
 }
 float flexmi_perf_metrics_get_accuracy(flexmi_perf_metrics_t pm) { return pm_float(pm, "get_accuracy"); }
 float flexmi_perf_metrics_get_loss(flexmi_perf_metrics_t pm) { return pm_float(pm, "get_loss"); }
+float flexmi_perf_metrics_get_auc(flexmi_perf_metrics_t pm) { return pm_float(pm, "get_auc"); }
+float flexmi_perf_metrics_get_auc_bound(flexmi_perf_metrics_t pm) { return pm_float(pm, "get_auc_bound"); }
 void flexmi_perf_metrics_destroy(flexmi_perf_metrics_t pm) { destroy(pm); }
 
 // ---------------------------------------------------------------------------------- data loaders

@@ -164,6 +164,10 @@ flexmi_initializer_t flexmi_norm_initializer_create(int seed, float mean, float 
 void flexmi_initializer_destroy(flexmi_initializer_t i);
 float flexmi_perf_metrics_get_accuracy(flexmi_perf_metrics_t pm);
 float flexmi_perf_metrics_get_loss(flexmi_perf_metrics_t pm);
+/* streaming ROC AUC and its bound on the distance from the exact AUC; NaN unless metric 1064
+ * (METRICS_AUC) was passed to flexmi_model_compile and both classes were seen */
+float flexmi_perf_metrics_get_auc(flexmi_perf_metrics_t pm);
+float flexmi_perf_metrics_get_auc_bound(flexmi_perf_metrics_t pm);
 void flexmi_perf_metrics_destroy(flexmi_perf_metrics_t pm);
 
 /* ---- data loaders ------------------------------------------------------------------------- */

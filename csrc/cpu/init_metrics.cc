@@ -17,6 +17,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <vector>
 
@@ -160,9 +161,57 @@ void loss_metrics(int64_t loss_type, torch::Tensor logits, torch::Tensor labels,
   for (int k = 0; k < NUM_SLOTS; ++k) ac[k] += (float)tot[k];
 }
 
+// METRICS_AUC histogram pass (same contract as csrc/kernels/auc.hip and auc_hist_torch):
+// hist[label >= 0.5][key(score) >> shift] += 1, NaN scores counted in invalid[0] only.  Each worker
+// counts its slice into a private (slot, count) list -- sorted and run-length folded, a batch touches
+// far fewer slots than the 2^21 of the histogram -- and the lists are merged under a lock at the end.
+void auc_hist(torch::Tensor scores, torch::Tensor labels, torch::Tensor hist, torch::Tensor invalid, int64_t shift) {
+  TORCH_CHECK(shift >= 1 && shift <= 31, "auc_hist: shift ", shift, " outside [1, 31]");
+  TORCH_CHECK(scores.device().is_cpu() && scores.scalar_type() == torch::kFloat32 && scores.is_contiguous(),
+              "auc_hist: contiguous fp32 CPU scores");
+  TORCH_CHECK(labels.device().is_cpu() && labels.numel() == scores.numel(), "auc_hist: one label per score");
+  const int64_t nb = (int64_t)1 << (32 - shift);
+  TORCH_CHECK(hist.device().is_cpu() && hist.scalar_type() == torch::kInt64 && hist.is_contiguous() && hist.numel() == 2 * nb,
+              "auc_hist: hist must be int64 [2, 1 << (32 - shift)]");
+  TORCH_CHECK(invalid.device().is_cpu() && invalid.scalar_type() == torch::kInt64 && invalid.numel() == 1, "auc_hist: invalid");
+  const int64_t B = scores.numel();
+  if (B == 0) return;
+  torch::Tensor lab = labels.to(torch::kFloat32).contiguous();
+  const float* sp = scores.data_ptr<float>();
+  const float* lp = lab.data_ptr<float>();
+  int64_t* h = hist.data_ptr<int64_t>();
+  int64_t bad_total = 0;
+  std::mutex mu;
+  at::parallel_for(0, B, 4096, [&](int64_t b0, int64_t b1) {
+    std::vector<uint32_t> slots;
+    slots.reserve((size_t)(b1 - b0));
+    int64_t bad = 0;
+    for (int64_t b = b0; b < b1; ++b) {
+      uint32_t u;
+      std::memcpy(&u, sp + b, 4);
+      if (u == 0x80000000u) u = 0u;                        // s + 0.0f
+      if ((u & 0x7fffffffu) > 0x7f800000u) { ++bad; continue; }
+      u = (u >> 31) ? ~u : (u | 0x80000000u);
+      slots.push_back((uint32_t)((lp[b] >= 0.5f ? nb : 0) + (int64_t)(u >> shift)));
+    }
+    std::sort(slots.begin(), slots.end());
+    std::lock_guard<std::mutex> lk(mu);
+    bad_total += bad;
+    for (size_t i = 0; i < slots.size();) {
+      size_t j = i + 1;
+      while (j < slots.size() && slots[j] == slots[i]) ++j;
+      h[slots[i]] += (int64_t)(j - i);
+      i = j;
+    }
+  });
+  invalid.data_ptr<int64_t>()[0] += bad_total;
+}
+
 }  // namespace
 
 void register_init_metrics(pybind11::module& m) {
+  m.def("auc_hist", &auc_hist, "METRICS_AUC score histogram (same contract as auc.hip)", pybind11::arg("scores"),
+        pybind11::arg("labels"), pybind11::arg("hist"), pybind11::arg("invalid"), pybind11::arg("shift"));
   m.def("counter_fill", &counter_fill, "counter-based init of a sub-box of a logical tensor (same values as init.hip)");
   m.def("loss_metrics", &loss_metrics, "loss gradient + metrics accumulation (same semantics as loss.hip)",
         pybind11::arg("loss_type"), pybind11::arg("logits"), pybind11::arg("labels"), pybind11::arg("grad"),

@@ -23,10 +23,17 @@ M_ALL, M_CORRECT, M_CCE, M_SCCE, M_MSE, M_RMSE, M_MAE, M_LOSS = range(8)
 NUM_SLOTS = 8
 
 
-class PerfMetrics:
-    """Host view of the folded metrics (``include/metrics_functions.h:26-40``)."""
+# METRICS_AUC: scores are binned by the top (32 - AUC_SHIFT) bits of a monotone integer key
+AUC_SHIFT = 12
+AUC_BINS = 1 << (32 - AUC_SHIFT)
 
-    def __init__(self, vals, metrics):
+
+class PerfMetrics:
+    """Host view of the folded metrics (``include/metrics_functions.h:26-40``).  ``auc`` (only when
+    METRICS_AUC was requested): ``(auc, bound, positives, negatives, invalid)`` of the folded score
+    histogram -- the exact sort-based AUC lies in [auc - bound, auc + bound]."""
+
+    def __init__(self, vals, metrics, auc=None):
         self.train_all = int(vals[M_ALL])
         self.train_correct = int(vals[M_CORRECT])
         self.cce_loss = float(vals[M_CCE])
@@ -36,6 +43,19 @@ class PerfMetrics:
         self.mae_loss = float(vals[M_MAE])
         self.loss_sum = float(vals[M_LOSS])
         self.metrics = metrics
+        self.has_auc = auc is not None
+        a = auc if auc is not None else (math.nan, math.nan, 0, 0, 0)
+        self.auc = float(a[0])
+        self.auc_bound = float(a[1])
+        self.auc_pos = int(a[2])
+        self.auc_neg = int(a[3])
+        self.auc_invalid = int(a[4])
+
+    def get_auc(self):
+        return self.auc
+
+    def get_auc_bound(self):
+        return self.auc_bound
 
     def get_accuracy(self):
         return 100.0 * self.train_correct / max(1, self.train_all)
@@ -62,6 +82,8 @@ class PerfMetrics:
             s += f" root_mean_squared_error: {self.rmse_loss / n:.4f}"
         if MetricsType.METRICS_MEAN_ABSOLUTE_ERROR in ms:
             s += f" mean_absolute_error: {self.mae_loss / n:.4f}"
+        if self.has_auc:
+            s += f" auc: {self.auc:.5f} (+-{self.auc_bound:.1e})"
         return s
 
 
@@ -76,6 +98,59 @@ def metrics_mask(metrics):
         if int(m) in ms:
             mask |= 1 << bit
     return mask
+
+
+def wants_auc(metrics):
+    return any(int(m) == int(MetricsType.METRICS_AUC) for m in (metrics or []))
+
+
+# ------------------------------------------------------------------ streaming ROC AUC
+# Contract (csrc/kernels/auc.hip, csrc/cpu/init_metrics.cc and the torch path below):
+#   x = s + 0.0f                  -0.0 becomes +0.0: they compare equal, so they share a bin
+#   u = bits(x); u = (u >> 31) ? ~u : (u | 0x80000000)      monotone total order, +-inf included
+#   bin = u >> shift              NaN scores are not binned but counted in ``invalid``
+# hist is int64 [2, 1 << (32 - shift)], row 0 negatives (label < 0.5), row 1 positives.
+def auc_keys(scores):
+    """int64 tensor of the 32-bit order keys of fp32 / bf16 scores (NaN keys are meaningless)."""
+    x = scores.detach().reshape(-1).float() + 0.0
+    u = x.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    return torch.where((u >> 31) != 0, u ^ 0xFFFFFFFF, u | 0x80000000)
+
+
+def auc_hist_torch(scores, labels, hist, invalid, shift=AUC_SHIFT):
+    """Torch implementation of the histogram pass (fallback path and test oracle)."""
+    x = scores.detach().reshape(-1).float()
+    ok = x == x
+    pos = labels.detach().reshape(-1).float() >= 0.5
+    nb = hist.shape[-1]
+    slot = (auc_keys(x) >> int(shift)) + pos.to(torch.int64) * nb
+    slot = slot[ok]
+    hist.view(-1).index_add_(0, slot, torch.ones_like(slot))
+    invalid += (~ok).sum()
+
+
+def auc_fold(hist):
+    """[sum pos*(2*cneg + neg), sum pos*neg, P, N] as one float64 tensor on hist's device: the
+    cumulative sum in int64, the products in float64, nothing copied to the host."""
+    neg, pos = hist[0], hist[1]
+    below = torch.cumsum(neg, 0) - neg
+    pd = pos.double()
+    return torch.stack([(pd * (2 * below + neg).double()).sum(), (pd * neg.double()).sum(),
+                        pos.sum().double(), neg.sum().double()])
+
+
+def auc_from_fold(f):
+    """(auc, bound, P, N) from the four host scalars of :func:`auc_fold`."""
+    num, tie, P, N = (float(v) for v in f)
+    if P == 0 or N == 0:
+        return math.nan, math.nan, int(P), int(N)
+    return num / (2.0 * P * N), tie / (2.0 * P * N), int(P), int(N)
+
+
+def auc_from_hist(hist):
+    """(auc, bound, P, N): pairs inside one bin count 1/2, so the exact AUC (ties 1/2) lies in
+    [auc - bound, auc + bound]; NaN when a class is missing."""
+    return auc_from_fold(auc_fold(hist).cpu())
 
 
 LOG_MIN = 1e-7
@@ -153,3 +228,4 @@ class Metrics:
         self.loss_type = LossType(loss_type)
         self.metrics = list(metrics or [])
         self.mask = metrics_mask(self.metrics)
+        self.auc = wants_auc(self.metrics)     # not a kernel mask bit: a histogram pass of its own

@@ -328,6 +328,14 @@ class FFModel:
             self.label_tensor = Tensor((final.dims[0], 1), DataType.DT_INT32, model=self, name="label")
         else:
             self.label_tensor = Tensor(final.dims, DataType.DT_FLOAT, model=self, name="label")
+        if self.metrics_op.auc:
+            # binary ROC AUC: one score per sample against a float label
+            per_sample = 1
+            for d in final.dims[1:]:
+                per_sample *= d
+            if self.loss_type == LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY or per_sample != 1:
+                raise ValueError(f"METRICS_AUC needs one score per sample and a float label; this model's output is "
+                                 f"{tuple(final.dims)} with loss {self.loss_type.name}")
         return self
 
     def init_layers(self):

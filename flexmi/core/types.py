@@ -55,6 +55,7 @@ class MetricsType(IntEnum):
     METRICS_MEAN_SQUARED_ERROR = 1008
     METRICS_ROOT_MEAN_SQUARED_ERROR = 1016
     METRICS_MEAN_ABSOLUTE_ERROR = 1032
+    METRICS_AUC = 1064      # flexmi extension: streaming ROC AUC (loss_metrics.py), not a per-sample sum
 
 
 class OperatorType(IntEnum):

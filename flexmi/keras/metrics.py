@@ -33,7 +33,12 @@ class MeanAbsoluteError(Metric):
     type = MetricsType.METRICS_MEAN_ABSOLUTE_ERROR
 
 
-_BY_NAME = {"accuracy": Accuracy, "categorical_crossentropy": CategoricalCrossentropy,
+class AUC(Metric):
+    """Streaming binary ROC AUC (flexmi extension; one sigmoid output, float labels)."""
+    type = MetricsType.METRICS_AUC
+
+
+_BY_NAME = {"accuracy": Accuracy, "auc": AUC, "categorical_crossentropy": CategoricalCrossentropy,
             "sparse_categorical_crossentropy": SparseCategoricalCrossentropy, "mean_squared_error": MeanSquaredError,
             "root_mean_squared_error": RootMeanSquaredError, "mean_absolute_error": MeanAbsoluteError}
 

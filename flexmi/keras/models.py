@@ -195,8 +195,12 @@ class Model:
                     cb.on_batch_end(it)
             pm = m.get_perf_metrics()
             history.append({"accuracy": pm.get_accuracy(), "loss": pm.get_loss()})
+            auc_s = ""
+            if pm.has_auc:
+                history[-1]["auc"] = pm.get_auc()
+                auc_s = f" auc {pm.get_auc():.5f} (+-{pm.get_auc_bound():.1e})"
             if verbose and self._ffconfig.rank == 0:
-                print(f"epoch {epoch}: accuracy {pm.get_accuracy():.2f}% loss {pm.get_loss():.4f}", file=sys.stderr)
+                print(f"epoch {epoch}: accuracy {pm.get_accuracy():.2f}% loss {pm.get_loss():.4f}{auc_s}", file=sys.stderr)
             stop = False
             for cb in callbacks:
                 stop = bool(cb.on_epoch_end(epoch)) or stop

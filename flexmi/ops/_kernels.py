@@ -338,6 +338,15 @@ def loss_forward_backward(loss_type, logits, labels, grad, scale, acc, mask, cla
     C().loss(loss_type, logits, labels, grad, scale, acc, mask, float(clamp))
 
 
+def auc_hist(scores, labels, hist, invalid, shift, rounds=-1):
+    """METRICS_AUC: hist[label >= 0.5][key(score) >> shift] += 1 per sample, NaN scores into ``invalid``
+    (csrc/kernels/auc.hip; the key is ``flexmi.core.loss_metrics.auc_keys``).  A wave folds
+    equal keys into one atomic each until ``rounds`` of its rounds found a key no other lane shares, then
+    its other lanes add 1 each; -1 is the kernel's default, 0 one atomic per sample, 64 the full peel
+    (tools/bench_auc.py)."""
+    C().auc_hist(scores, labels, hist, invalid, int(shift), int(rounds))
+
+
 # ------------------------------------------------------------------ element-wise & data movement
 def unary_forward(code, x, y):
     C().unary_fwd(code, x, y)

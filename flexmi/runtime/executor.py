@@ -26,7 +26,8 @@ from typing import Dict, List
 import numpy as np
 import torch
 
-from flexmi.core.loss_metrics import NUM_SLOTS, PerfMetrics, loss_and_metrics_torch
+from flexmi.core.loss_metrics import (AUC_BINS, AUC_SHIFT, NUM_SLOTS, PerfMetrics, auc_fold, auc_from_fold,
+                                      auc_hist_torch, loss_and_metrics_torch)
 from flexmi.core.initializers import _native_cpu
 from flexmi.core.optimizers import SGDOptimizer
 from flexmi.core.types import DataType, LossType, to_torch_dtype
@@ -1375,6 +1376,13 @@ class Executor:
                 self.label_buf.zero_()
             self.act[(lab.guid, self.label_layout.key())] = self.label_buf
         self.metric_acc = torch.zeros(NUM_SLOTS, dtype=torch.float32, device=self.device)
+        # METRICS_AUC state: int64 score histogram [2, AUC_BINS] (row 0 negatives, row 1 positives)
+        # and the NaN counter, one buffer so that one all-reduce folds both; only when requested
+        self.auc_state = self.auc_hist = self.auc_invalid = None
+        if self.metrics_obj is not None and getattr(self.metrics_obj, "auc", False):
+            self.auc_state = torch.zeros(2 * AUC_BINS + 1, dtype=torch.int64, device=self.device)
+            self.auc_hist = self.auc_state[:2 * AUC_BINS].view(2, AUC_BINS)
+            self.auc_invalid = self.auc_state[2 * AUC_BINS:]
 
     def gkey(self, g):
         while g in self.galias:
@@ -2192,6 +2200,20 @@ class Executor:
         else:
             loss_and_metrics_torch(self.loss_type, self.logits_buf, self.label_buf, self.logit_grad,
                                    scale, self.metric_acc, mask, compute_grad, clamp=clamp)
+        if self.auc_hist is not None:
+            self._auc_kernel()
+
+    def _auc_kernel(self):
+        """METRICS_AUC: bin this rank's raw scores (no --loss-threshold clamp: it would manufacture
+        ties) right after the loss kernel, inside the same program item."""
+        if self.backend == "hip":
+            from flexmi.ops import _kernels as K
+            K.auc_hist(self.logits_buf, self.label_buf, self.auc_hist, self.auc_invalid, AUC_SHIFT)
+        elif (_native_cpu() is not None and self.logits_buf.dtype == torch.float32 and self.logits_buf.is_contiguous()
+              and self.auc_hist.device.type == "cpu"):
+            _native_cpu().auc_hist(self.logits_buf, self.label_buf, self.auc_hist, self.auc_invalid, AUC_SHIFT)
+        else:
+            auc_hist_torch(self.logits_buf, self.label_buf, self.auc_hist, self.auc_invalid, AUC_SHIFT)
 
     def compute_metrics(self):
         if not hasattr(self, "prog_metrics"):
@@ -2201,12 +2223,28 @@ class Executor:
 
     def reset_metrics(self):
         self.metric_acc.zero_()
+        if self.auc_state is not None:
+            self.auc_state.zero_()
+
+    def auc_hist_folded(self):
+        """(hist [2, AUC_BINS], invalid [1]) summed over all ranks: integer sums, so every rank sees
+        the same state however the samples were spread.  A clone at world > 1, the live state else."""
+        st = self.auc_state
+        if self.world > 1:
+            st = self.comm.all_reduce(st.clone())
+        return st[:2 * AUC_BINS].view(2, AUC_BINS), st[2 * AUC_BINS:]
 
     def perf_metrics(self):
         acc = self.metric_acc.clone()
         if self.world > 1:
             self.comm.all_reduce(acc)
-        return PerfMetrics(acc.cpu().double().numpy(), self.metrics_obj.metrics if self.metrics_obj else [])
+        auc = None
+        if self.auc_state is not None:
+            # folded on the device: only five scalars reach the host
+            hist, inv = self.auc_hist_folded()
+            f = torch.cat([auc_fold(hist), inv.double()]).cpu()
+            auc = auc_from_fold(f[:4]) + (int(f[4]),)
+        return PerfMetrics(acc.cpu().double().numpy(), self.metrics_obj.metrics if self.metrics_obj else [], auc)
 
     # ------------------------------------------------------------------ host views
     def _gather_full(self, lay: Layout, local, dtype):

@@ -109,6 +109,9 @@ class MetricsLogger:
         if perf is not None:
             rec["loss"] = perf.get_loss()
             rec["accuracy"] = perf.get_accuracy()
+            if getattr(perf, "has_auc", False):
+                rec["auc"] = perf.get_auc()
+                rec["auc_bound"] = perf.get_auc_bound()
         if executor is not None:
             rec["comm_calls"] = executor.comm.calls
             rec["comm_bytes"] = executor.comm.bytes_sent
