@@ -12,8 +12,10 @@ ring, ``HDF5DLRMData``), otherwise on random data of ``--data-size`` samples (de
 GPUs, dlrm.cc:273-282); ``--loss-threshold t`` clamps predictions to [t, 1-t] in the loss.  The
 loop is the reference's (dlrm.cc:160-195): per epoch ``num_samples / batch`` iterations of
 next_batch / forward / zero_gradients / backward / update, traced with begin/end_trace(111),
-then ``ELAPSED TIME = ..., THROUGHPUT = ... samples/s``.  ``--preset`` (mlperf, run_random,
-criteo_kaggle, summit, summit_large, kaggle_day1, tiny) seeds the architecture flags.
+then ``ELAPSED TIME = ..., THROUGHPUT = ... samples/s``.  ``--preset`` (mlperf, mlperf_dcnv2, run_random,
+criteo_kaggle, summit, summit_large, kaggle_day1, tiny, tiny_dcn) seeds the architecture flags.
+``--arch-interaction-op dcn`` (flexmi extension, with ``--arch-dcn-layers N`` and ``--arch-dcn-rank R``) puts N
+DCNv2 low-rank cross layers between the concatenation and the top MLP (MLPerf DLRM-DCNv2).
 ``--optimizer {sgd,adagrad,rowwise_adagrad}`` (flexmi extension, default sgd): Adagrad keeps one
 accumulator per table element and updates non-replicated tables sparsely; row-wise Adagrad keeps
 one per table ROW and trains every table sparsely, replicated ones included

@@ -104,6 +104,9 @@ void fm_binary_forward(int code, const void* a, const void* b, void* y, long n, 
 void fm_binary_backward(int code, const void* a, const void* b, const void* dy, const void* ymask, void* da, void* db,
                         long n, int acca, int accb, int bf16, hipStream_t s);
 void fm_act_bwd_bias(const void* y, const void* dy, void* dpre, float* db, long B, int N, int act, int bf16, hipStream_t s);
+void fm_cross_forward(const void* x0, const void* t, const void* x, void* y, long n, int bf16, hipStream_t s);
+void fm_cross_backward(const void* dy, const void* x0, const void* t, void* dt, void* dx0, void* dx, long n, int acct, int acc0,
+                       int accx, int self, int bf16, hipStream_t s);
 void fm_multi_copy2d(int n, const void* const* src, void* const* dst, const long* rows, const long* cols, const long* lds,
                      const long* ldd, int add_mask, int elem_bytes, hipStream_t s);
 void fm_permute_nd(const void* x, void* y, int nd, const long* out_dims, const long* in_strides_perm, int acc, int bf16,
@@ -903,6 +906,38 @@ void binary_bwd(int64_t code, torch::Tensor a, torch::Tensor b, torch::Tensor dy
   fm_binary_backward((int)code, a.data_ptr(), b.data_ptr(), dy.data_ptr(), cptr(ymask), mptr(da), mptr(db), a.numel(), acca,
                      accb, is_bf16(a), cur());
 }
+// DCNv2 cross combine (cross.hip).  The kernels index every operand as a flat array of ref's length:
+// each one given must be a contiguous device tensor of ref's dtype and element count
+static void cross_operand(const torch::Tensor& ref, const c10::optional<torch::Tensor>& t, const char* what) {
+  if (!t.has_value() || !t->defined()) return;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == ref.scalar_type() && t->numel() == ref.numel(), what,
+              ": contiguous device tensor of the first operand's dtype and size expected");
+}
+// y = x0 * t + x; without x (the first layer, x_l = x_0): y = x0 * t + x0
+void cross_fwd(torch::Tensor x0, torch::Tensor t, c10::optional<torch::Tensor> x, torch::Tensor y) {
+  TORCH_CHECK(x0.is_cuda() && x0.is_contiguous() &&
+                  (x0.scalar_type() == torch::kBFloat16 || x0.scalar_type() == torch::kFloat32),
+              "cross_fwd: contiguous bf16 or fp32 device tensors");
+  cross_operand(x0, t, "cross_fwd t");
+  cross_operand(x0, x, "cross_fwd x");
+  cross_operand(x0, y, "cross_fwd y");
+  fm_cross_forward(x0.data_ptr(), t.data_ptr(), cptr(x), y.data_ptr(), x0.numel(), is_bf16(x0), cur());
+}
+// dt (+)= dy * x0, dx0 (+)= dy * t (+ dy when self: the form without x), dx (+)= dy; absent outputs are skipped
+void cross_bwd(torch::Tensor dy, torch::Tensor x0, torch::Tensor t, c10::optional<torch::Tensor> dt,
+               c10::optional<torch::Tensor> dx0, c10::optional<torch::Tensor> dx, bool acct, bool acc0, bool accx, bool self) {
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() &&
+                  (dy.scalar_type() == torch::kBFloat16 || dy.scalar_type() == torch::kFloat32),
+              "cross_bwd: contiguous bf16 or fp32 device tensors");
+  cross_operand(dy, x0, "cross_bwd x0");
+  cross_operand(dy, t, "cross_bwd t");
+  cross_operand(dy, dt, "cross_bwd dt");
+  cross_operand(dy, dx0, "cross_bwd dx0");
+  cross_operand(dy, dx, "cross_bwd dx");
+  TORCH_CHECK(!(self && mptr(dx)), "cross_bwd: the form without x has no dx");
+  fm_cross_backward(dy.data_ptr(), x0.data_ptr(), t.data_ptr(), mptr(dt), mptr(dx0), mptr(dx), dy.numel(), acct, acc0, accx,
+                    self, is_bf16(dy), cur());
+}
 void act_bwd_bias(torch::Tensor y, torch::Tensor dy, c10::optional<torch::Tensor> dpre, c10::optional<torch::Tensor> db,
                   int64_t B, int64_t N, int64_t act) {
   TORCH_CHECK(y.scalar_type() == dy.scalar_type() && (y.scalar_type() == torch::kBFloat16 || y.scalar_type() == torch::kFloat32),
@@ -1518,6 +1553,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("unary_bwd", &unary_bwd);
   m.def("binary_fwd", &binary_fwd);
   m.def("binary_bwd", &binary_bwd);
+  m.def("cross_fwd", &cross_fwd);
+  m.def("cross_bwd", &cross_bwd);
   m.def("act_bwd_bias", &act_bwd_bias);
   m.def("multi_copy", &multi_copy);
   m.def("image_normalize", &image_normalize);

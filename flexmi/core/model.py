@@ -23,6 +23,7 @@ from flexmi.core.tensor import Parameter, Tensor
 from flexmi.core.types import (ActiMode, AggrMode, DataType, LossType, MetricsType, OperatorType,
                                PoolType)
 from flexmi.ops.conv import BatchNorm, Conv2D, Pool2D
+from flexmi.ops.cross import CrossCombine
 from flexmi.ops.elementwise import ElementBinary, ElementUnary
 from flexmi.ops.embedding import Embedding
 from flexmi.ops.linear import Linear
@@ -267,6 +268,32 @@ class FFModel:
     def dot_interaction(self, bottom, embs, self_interaction=False, name=None):
         """DLRM ``dot`` feature interaction (fixes reference caveat C3)."""
         return self._add(DotInteraction(self, bottom, embs, 16, self_interaction, name)).outputs[0]
+
+    def cross_combine(self, x0, t, x=None, name=None):
+        """``y = x0 * t + x`` in one pass (DCNv2 cross-layer combine).  ``x=None`` is the first
+        layer's form ``y = x0 * t + x0``; passing ``x0`` itself as ``x`` is rejected."""
+        return self._add(CrossCombine(self, x0, t, x, name)).outputs[0]
+
+    def cross_layer(self, x0, x, rank, kernel_initializer=None, bias_initializer=None, name=None):
+        """One DCNv2 low-rank cross layer ``x0 * (U (V x) + b) + x``: ``V`` [rank, D] and ``U`` [D, rank]
+        are ordinary Linear ops (no activation; only ``U`` has the bias), then :meth:`cross_combine`.
+        Defaults follow torchrec's ``LowRankCrossNet`` with ``create_mlp``'s formula: both kernels
+        N(0, sqrt(2 / (fan_in + fan_out))), zero bias.  ``kernel_initializer`` is one initializer for
+        both kernels or a ``(V, U)`` pair."""
+        import math
+        from flexmi.core.initializers import NormInitializer, ZeroInitializer
+        D = x.dims[-1]
+        if isinstance(kernel_initializer, (tuple, list)):
+            vinit, uinit = kernel_initializer
+        else:
+            vinit = uinit = kernel_initializer
+        std = math.sqrt(2.0 / (D + rank))
+        vinit = vinit or NormInitializer(self._next_seed(), 0.0, std)
+        uinit = uinit or NormInitializer(self._next_seed(), 0.0, std)
+        pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
+        v = self.dense(x, rank, ActiMode.AC_MODE_NONE, False, None, vinit, None, pre("v"))
+        t = self.dense(v, D, ActiMode.AC_MODE_NONE, True, None, uinit, bias_initializer or ZeroInitializer(), pre("u"))
+        return self.cross_combine(x0, t, None if x is x0 else x, name)
 
     def _share(self, op, shared_op):
         """``shared_op`` (``src/runtime/model.cc:157-171``): the new op uses the weights of

@@ -128,6 +128,7 @@ class OperatorType(IntEnum):
     OP_LSTM = 101
     OP_EMBEDDING_COLLECTION = 102
     OP_MSELOSS = 103
+    OP_CROSS_COMBINE = 104
 
 
 class OpType(IntEnum):

@@ -1,8 +1,12 @@
 """DLRM (the reference's headline workload, ``examples/cpp/DLRM/dlrm.cc:26-199``).
 
 Graph: dense input -> bottom MLP; every sparse feature -> embedding bag; feature interaction
-(``cat`` as in the reference, or ``dot`` -- the DLRM/MLPerf interaction the reference left as a
-TODO, caveat C3); top MLP ending in a sigmoid; MSE (reference) or BCE (MLPerf) loss; SGD.
+(``cat`` as in the reference, ``dot`` -- the DLRM/MLPerf interaction the reference left as a
+TODO, caveat C3 -- or ``dcn``: the concatenation followed by ``dcn_layers`` DCNv2 low-rank cross
+layers ``x_{l+1} = x_0 * (U_l (V_l x_l) + b_l) + x_l`` of rank ``dcn_rank``, the interaction of
+MLPerf's DLRM-DCNv2 since v3.0, ``FFModel.cross_layer``); top MLP ending in a sigmoid; MSE
+(reference) or BCE (MLPerf) loss; SGD.  The bag size is one number for every table (the MLPerf
+DCNv2 data set has per-table multi-hot sizes: not provided).
 Initialisers follow ``create_mlp``/``create_emb`` (``dlrm.cc:26-47``): MLP weights
 N(0, sqrt(2/(in+out))), biases N(0, sqrt(2/out)), tables U(±sqrt(1/rows)).
 
@@ -48,6 +52,8 @@ class DLRMConfig:
     data_size: int = -1
     loss: str = "mse"            # mse (reference) | bce (MLPerf)
     name: str = "custom"
+    dcn_layers: int = 3          # arch_interaction_op == "dcn": cross layers ...
+    dcn_rank: int = 512          # ... and their rank
 
     @staticmethod
     def preset(name):
@@ -57,6 +63,9 @@ class DLRMConfig:
         if name == "mlperf":      # MLPerf DLRM (Criteo Terabyte): 13 dense + 26 sparse, dot, d=128
             return DLRMConfig(128, list(MLPERF_TABLES), [13, 512, 256, 128], [479, 1024, 1024, 512, 256, 1], 1, -1, -1,
                               0.0, "dot", "", -1, "bce", "mlperf")
+        if name == "mlperf_dcnv2":  # MLPerf DLRM-DCNv2 (v3.0 on): 3 cross layers of rank 512 over [x] + 26 tables
+            return DLRMConfig(128, list(MLPERF_TABLES), [13, 512, 256, 128], [3456, 1024, 1024, 512, 256, 1], 1, -1, -1,
+                              0.0, "dcn", "", -1, "bce", "mlperf_dcnv2", 3, 512)
         if name == "criteo_kaggle":  # run_criteo_kaggle.sh
             return DLRMConfig(16, list(KAGGLE_TABLES), [13, 512, 256, 64, 16], [224, 512, 256, 1], 1, -1, -1, 0.0,
                               "cat", "", -1, "mse", "criteo_kaggle")
@@ -72,6 +81,9 @@ class DLRMConfig:
                               "cat", "", -1, "mse", "kaggle_day1")
         if name == "tiny":
             return DLRMConfig(16, [100, 50, 200, 30], [13, 32, 16], [64, 32, 1], 1, -1, -1, 0.0, "dot", "", -1, "bce", "tiny")
+        if name == "tiny_dcn":
+            return DLRMConfig(16, [100, 50, 200, 30], [13, 32, 16], [80, 32, 1], 1, -1, -1, 0.0, "dcn", "", -1, "bce",
+                              "tiny_dcn", 2, 8)
         raise KeyError(name)
 
     @staticmethod
@@ -100,6 +112,10 @@ class DLRMConfig:
                 c.sigmoid_bot = int(nx); i += 1
             elif a == "--arch-interaction-op":
                 c.arch_interaction_op = nx; i += 1
+            elif a == "--arch-dcn-layers":
+                c.dcn_layers = int(nx); i += 1
+            elif a == "--arch-dcn-rank":
+                c.dcn_rank = int(nx); i += 1
             elif a == "--dataset":
                 c.dataset_path = nx; i += 1
             elif a == "--data-size":
@@ -153,6 +169,10 @@ def build_dlrm(model, c: DLRMConfig, pad_dense=True):
         z = model.concat([x] + ly, 1, name="concat")
     elif c.arch_interaction_op == "dot":
         z = model.dot_interaction(x, ly, name="interaction")
+    elif c.arch_interaction_op == "dcn":
+        z0 = z = model.concat([x] + ly, 1, name="concat")
+        for l in range(c.dcn_layers):
+            z = model.cross_layer(z0, z, c.dcn_rank, name=f"cross{l}")
     else:
         raise ValueError(c.arch_interaction_op)
     top = [z.dims[1]] + list(c.mlp_top[1:])

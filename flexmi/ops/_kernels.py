@@ -364,6 +364,17 @@ def binary_backward(code, a, b, dy, da, db, acca, accb, ymask=None):
     C().binary_bwd(code, a, b, dy, ymask, da, db, bool(acca), bool(accb))
 
 
+def cross_forward(x0, t, x, y):
+    """DCNv2 combine ``y = x0 * t + x`` in one pass (csrc/kernels/cross.hip); ``x=None``: ``+ x0``."""
+    C().cross_fwd(x0, t, x, y)
+
+
+def cross_backward(dy, x0, t, dt, dx0, dx, acct, acc0, accx, self_form):
+    """``dt (+)= dy * x0``, ``dx0 (+)= dy * t`` (``+ dy`` in the form without x), ``dx (+)= dy`` in
+    one pass over dy; a ``None`` output is skipped."""
+    C().cross_bwd(dy, x0, t, dt, dx0, dx, bool(acct), bool(acc0), bool(accx), bool(self_form))
+
+
 def _outer_inner(shape, axis):
     outer = 1
     for d in shape[:axis]:

@@ -114,7 +114,7 @@ class SearchResult:
 
 def _rowwise(op):
     """Ops the executor runs as micro-batch chunks in a pipelined tail (Executor._plan_pipeline)."""
-    return op.op_type in (OperatorType.OP_LINEAR, OperatorType.OP_DOT_INTERACTION) or (
+    return op.op_type in (OperatorType.OP_LINEAR, OperatorType.OP_DOT_INTERACTION, OperatorType.OP_CROSS_COMBINE) or (
         op.op_type == OperatorType.OP_CONCAT and op.axis != 0)
 
 

@@ -1403,7 +1403,7 @@ class Executor:
         """The chunked tail of XCHG_CHUNKS, or None.  Decided from global layouts only (every rank
         takes the same decision: the chunk all-to-alls are collectives).  Conditions: the last
         cross-device forward exchange is followed by ops only; each is a row-wise kind (Linear,
-        DotInteraction, Concat off the sample dim) whose outputs and needed inputs are one-holder sample splits over the
+        DotInteraction, CrossCombine, Concat off the sample dim) whose outputs and needed inputs are one-holder sample splits over the
         whole world with identical per-rank rows; every rank holds >= 8 rows per chunk."""
         from flexmi.core.types import OperatorType
         if self.world == 1 and not XCHG_LOCAL:
@@ -1412,7 +1412,8 @@ class Executor:
         W = self.world
 
         def rowwise(op):
-            return op.op_type in (OperatorType.OP_LINEAR, OperatorType.OP_DOT_INTERACTION) or (
+            return op.op_type in (OperatorType.OP_LINEAR, OperatorType.OP_DOT_INTERACTION,
+                                  OperatorType.OP_CROSS_COMBINE) or (
                 op.op_type == OperatorType.OP_CONCAT and op.axis != 0)
 
         xk = [k for k, st in enumerate(steps)

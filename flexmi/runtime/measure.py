@@ -28,6 +28,8 @@ def _make_clone(op, m, in_shapes, out_shapes):
         m.embedding(ins[0], op.num_entries, out_shapes[0][-1], op.aggr)
     elif t == OperatorType.OP_DOT_INTERACTION:
         m.dot_interaction(ins[0], ins[1:], op.self_interaction)
+    elif t == OperatorType.OP_CROSS_COMBINE:
+        m.cross_combine(ins[0], ins[1], ins[2] if len(ins) > 2 else None)
     elif t == OperatorType.OP_CONCAT:
         m.concat(ins, op.axis)
     elif t == OperatorType.OP_BATCHMATMUL:
