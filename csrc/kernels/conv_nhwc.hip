@@ -33,8 +33,6 @@
 #include <algorithm>
 #include <type_traits>
 
-extern "C" int fm_gemm_dma_enabled();   // gemm_f32.hip
-
 namespace {
 
 constexpr unsigned OOBN = 0x80000000u;   // buffer offset past num_records: the load returns 0

@@ -16,14 +16,12 @@
 // (one barrier per K-tile).  The MFMA operands are swapped (B fragment as the MFMA "A") so each
 // lane ends up owning 4 consecutive output COLUMNS -> 8-B/16-B vector stores in the epilogue.
 // Epilogue: alpha, fp32 bias[n], activation (relu/sigmoid/tanh), beta=1 accumulate, bf16 or
-// fp32 output.  Split-K writes fp32 slabs reduced by fm_gemm_splitk_reduce (same epilogue).
+// fp32 output.  Split-K writes fp32 slabs reduced by fm_gemm_reduce (same output rule, gemm_epilogue.h).
 // Blocks are remapped so consecutive tiles share an XCD (private 4 MB L2 per XCD).
-#include "gemm_common.h"
+#include "gemm_epilogue.h"
 
 #include <algorithm>
 #include <cstdlib>
-
-extern "C" int fm_gemm_dma_enabled();   // gemm_f32.hip
 
 namespace {
 
@@ -97,9 +95,6 @@ struct Stage {
   }
 };
 
-typedef __attribute__((address_space(1))) const void* gptr_b;
-typedef __attribute__((address_space(3))) void* lptr_b;
-
 // ---- global -> LDS by LDS-DMA (global_load_lds: no VGPR round trip, no ds_write) ------------
 // One wave-instruction fills 1 KiB of the operand image: lane L's 16 B land at base + 16 L, so each
 // lane loads the global chunk that the image's swizzle puts there (the inverse of lds_off).  Full
@@ -125,54 +120,12 @@ struct DmaStage {
         const int c = slot ^ MNSwz<R>::f(kr);
         src = p + (long)(k0 + kr) * ld + row0 + 8 * c;
       }
-      __builtin_amdgcn_global_load_lds((gptr_b)(const void*)src, (lptr_b)(void*)(lds + piece * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gptr_t)(const void*)src, (lptr_t)(void*)(lds + piece * 1024), 16, 0, 0);
     }
   }
 };
 
 // NTH = 256: 4 waves (2x2, wave tile BM/2 x BN/2); 512: 8 waves (2x4 for BN >= 128, else 4x2).
-// Fused-SGD epilogue of an unsplit dW tile, staged through LDS: the accumulator layout gives each
-// lane 4 columns of one row, i.e. 64-B row pieces per 16x16 tile -- a scattered pattern that held the
-// W read-modify-write (fp32 master + bf16 mirror, ~10 B per element) at ~2.8 TB/s.  The waves first
-// park the BM x BN fp32 tile in the (free) operand LDS, 16-B chunks XOR-swizzled by row so both the
-// accumulator writes and the row reads stay conflict-light, then every wave updates whole rows:
-// BN*4 contiguous bytes of W per row (512 B for BN = 128).  The tile fits the K-loop LDS exactly
-// (BM*BN*4 <= 2*(BM+BN)*BK*2).
-template <int BM, int BN, int NTH, int MR, int NR>
-FM_DEVICE void sgd_epilogue_lds(const GemmP& p, const f32x4_t (&acc)[MR][NR], char* smem, int m0, int n0, int mb,
-                                int nb, int lane, int tid) {
-  constexpr int CPR = BN / 4;                       // 16-B chunks per tile row
-  static_assert(BM * BN * 4 <= 2 * (BM + BN) * BK * 2, "fp32 tile must fit the K-loop LDS");
-  static_assert(CPR >= 8, "row XOR swizzle (r & 7) needs >= 8 chunks per row");
-  f32x4_t* t = reinterpret_cast<f32x4_t*>(smem);
-  __syncthreads();                                  // every wave is done with the operand tiles
-#pragma unroll
-  for (int i = 0; i < MR; ++i)
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const int r = mb + 16 * i + (lane & 15);
-      const int c = (nb + 16 * j + 4 * (lane >> 4)) >> 2;
-      t[r * CPR + (c ^ (r & 7))] = acc[i][j] * p.alpha;
-    }
-  __syncthreads();
-  const bool n4 = (p.N & 3) == 0;
-#pragma unroll 4
-  for (int q = tid; q < BM * CPR; q += NTH) {
-    const int r = q / CPR, c = q % CPR;
-    const int m = m0 + r, n = n0 + 4 * c;
-    if (m >= p.M || n >= p.N) continue;
-    const f32x4_t g = t[r * CPR + (c ^ (r & 7))];
-    const long o = (long)m * p.ldc + n;
-    if (n4 && n + 3 < p.N) {
-      sgd_apply4(p, o, g);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (n + e < p.N) sgd_apply1(p, o + e, g[e]);
-    }
-  }
-}
-
 template <int BM, int BN, bool AK, bool BKC, bool VEC, int NTH = NT, bool SGD = false, bool DMA = false>
 __global__ void __launch_bounds__(NTH, 2) fm_gemm_kernel(GemmP p) {
   constexpr int A_BYTES = BM * BK * 2;
@@ -194,8 +147,8 @@ __global__ void __launch_bounds__(NTH, 2) fm_gemm_kernel(GemmP p) {
 
   // XCD-aware bijective remap of the tile id (blocks b and b+8 share an XCD)
   const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
-  int tm, tn;
-  tile_coords(p, bid, tm, tn);
+  const TileMN tile = tile_coords(p, bid);
+  const int tm = tile.m, tn = tile.n;
   const int zb = blockIdx.y;           // batch
   const int split = blockIdx.z;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -313,129 +266,12 @@ __global__ void __launch_bounds__(NTH, 2) fm_gemm_kernel(GemmP p) {
 #undef LDS_B
   if constexpr (SGD) {
     if (p.ksplit == 1 && p.ulds) {
-      sgd_epilogue_lds<BM, BN, NTH, MR, NR>(p, acc, smem, m0, n0, wm * TM, wn * TN, lane, tid);
+      sgd_epilogue_lds<BM, BN, NTH, MR, NR, false, false, 2 * (A_BYTES + B_BYTES)>(p, acc, smem, m0, n0, m0 + wm * TM,
+                                                                                   n0 + wn * TN, lane, tid);
       return;
     }
   }
-  gemm_epilogue<MR, NR, SGD>(p, acc, zb, split, m0 + wm * TM, n0 + wn * TN, lane);
-}
-
-template <bool SGD>
-__global__ void fm_gemm_splitk_reduce(GemmP p);
-
-// 4 consecutive outputs per thread (16-B slab loads): N % 4 == 0, fp32 C with ldc % 4 == 0
-template <bool SGD>
-__global__ void fm_gemm_splitk_reduce4(GemmP p) {
-  const long MN = (long)p.M * p.N;
-  const long total4 = MN * p.batch / 4;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
-    const long e4 = i * 4;
-    const long zb = e4 / MN, e = e4 % MN;
-    const int m = (int)(e / p.N), n = (int)(e % p.N);
-    const float* src = p.ws + zb * p.ksplit * MN + e;
-    f32x4_t s = slab_sum4(src, MN, p.ksplit);
-    s *= p.alpha;
-    if constexpr (SGD) {
-      sgd_apply4(p, (long)m * p.ldc + n, s);
-      continue;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) s[r] = act_fwd(p.act, s[r] + (p.bias ? p.bias[n + r] : 0.f));
-    f32x4_t* d = reinterpret_cast<f32x4_t*>(reinterpret_cast<float*>(p.C) + zb * p.sC + (long)m * p.ldc + n);
-    if (p.beta) s += *d;
-    *d = s;
-  }
-}
-
-}  // namespace
-
-
-namespace {
-
-void launch_splitk_reduce(const GemmP& p, hipStream_t stream) {
-  const long total = (long)p.M * p.N * p.batch;
-  const bool v4 = p.c_fp32 && (p.N % 4 == 0) && (p.ldc % 4 == 0) && (p.sC % 4 == 0) &&
-                  ((((uintptr_t)p.C) & 15) == 0);
-  if (p.uw) {
-    if (v4) hipLaunchKernelGGL(fm_gemm_splitk_reduce4<true>, dim3(fm_grid(total / 4)), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(fm_gemm_splitk_reduce<true>, dim3(fm_grid(total)), dim3(256), 0, stream, p);
-  } else {
-    if (v4) hipLaunchKernelGGL(fm_gemm_splitk_reduce4<false>, dim3(fm_grid(total / 4)), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(fm_gemm_splitk_reduce<false>, dim3(fm_grid(total)), dim3(256), 0, stream, p);
-  }
-}
-
-template <bool SGD>
-__global__ void fm_gemm_splitk_reduce(GemmP p) {
-  const long MN = (long)p.M * p.N;
-  const long total = MN * p.batch;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    long zb = i / MN, e = i % MN;
-    int m = (int)(e / p.N), n = (int)(e % p.N);
-    const float* src = p.ws + zb * p.ksplit * MN + e;
-    float s = slab_sum1(src, MN, p.ksplit);
-    float v = s * p.alpha;
-    if constexpr (SGD) {
-      sgd_apply1(p, (long)m * p.ldc + n, v);
-      continue;
-    }
-    if (p.bias) v += p.bias[n];
-    v = act_fwd(p.act, v);
-    long ci = zb * p.sC + (long)m * p.ldc + n;
-    if (p.c_fp32) {
-      float* d = reinterpret_cast<float*>(p.C) + ci;
-      *d = v + (p.beta ? *d : 0.f);
-    } else {
-      unsigned short* d = reinterpret_cast<unsigned short*>(p.C) + ci;
-      *d = f2bf(v + (p.beta ? bf2f(*d) : 0.f));
-    }
-  }
-}
-
-// split-K reduce with the FUSED BACKWARD epilogue (bf16 act_y): v = act_bwd(bact, ay, act(alpha*sum +
-// bias)), colsum[n] += column sums of v.  Thread = 4 columns x RB rows (one atomic per column and
-// block); lets small-batch dX GEMMs split K (summit_large 256 x 4096 x 4096).
-__global__ void __launch_bounds__(256) fm_gemm_splitk_reduce_bwd(GemmP p, int RB) {
-  const int n = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (n >= p.N) return;
-  const int m0 = blockIdx.y * RB, m1 = min(p.M, m0 + RB);
-  const long MN = (long)p.M * p.N;
-  const bool v4 = n + 3 < p.N && (p.N & 3) == 0;
-  float cs[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int m = m0; m < m1; ++m) {
-    const float* src = p.ws + (long)m * p.N + n;
-    float sv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (v4) {
-      f32x4_t a = slab_sum4(src, MN, p.ksplit);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sv[r] = a[r];
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (n + r < p.N)
-          sv[r] = slab_sum1(src + r, MN, p.ksplit);
-    }
-    const long ci = (long)m * p.ldc + n;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (n + r >= p.N) break;
-      float v = act_fwd(p.act, sv[r] * p.alpha + (p.bias ? p.bias[n + r] : 0.f));
-      if (p.ay) v = act_bwd(p.bact, bf2f(p.ay[(long)m * p.lday + n + r]), v);
-      cs[r] += v;                               // as the in-tile epilogue: the unrounded value
-      if (p.c_fp32) {
-        float* d = reinterpret_cast<float*>(p.C) + ci + r;
-        *d = v + (p.beta ? *d : 0.f);
-      } else {
-        unsigned short* d = reinterpret_cast<unsigned short*>(p.C) + ci + r;
-        *d = f2bf(v + (p.beta ? bf2f(*d) : 0.f));
-      }
-    }
-  }
-  if (p.colsum) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (n + r < p.N) atomicAdd(p.colsum + n + r, cs[r]);
-  }
+  gemm_epilogue<MR, NR, false, false, SGD>(p, acc, zb, split, m0 + wm * TM, n0 + wn * TN, lane);
 }
 
 template <int BM, int BN, bool AK, bool BKC, bool VEC>
@@ -488,10 +324,6 @@ void launch_bm(const GemmP& p, bool ak, bool bk, bool vec, hipStream_t s) {
 
 // A_kcontig: A stored [M][K] (lda >= K) else [K][M] (lda >= M)
 // B_kcontig: B stored [N][K] (ldb >= K) else [K][N] (ldb >= N)
-struct SgdUpd {
-  float* w; unsigned short* wc; float* v; const float* lr; float wd, mom; int nest;
-};
-
 static int gemm_run(const void* A, long lda, long sA, int a_kcontig,
                     const void* B, long ldb, long sB, int b_kcontig,
                     void* C, long ldc, long sC, int c_fp32,
@@ -532,9 +364,7 @@ static int gemm_run(const void* A, long lda, long sA, int a_kcontig,
                     const void* act_y, long lday, int bwd_act, float* colsum, float* rowsum_a,
                     const SgdUpd* upd, hipStream_t stream) {
   if (M <= 0 || N <= 0 || batch <= 0) return 0;
-  if (upd && (K <= 0 || ldc % 4 != 0 || (((uintptr_t)upd->w | (uintptr_t)(upd->v ? upd->v : upd->w)) & 15) ||
-              (((uintptr_t)(upd->wc ? (void*)upd->wc : (void*)upd->w)) & 7)))
-    return -1;                         // the caller computes the gradient and runs the update itself
+  if (upd && !sgd_upd_ok(*upd, K, ldc)) return -1;   // the caller computes the gradient and runs the update itself
   GemmP p;
   p.A = (const unsigned short*)A; p.lda = lda; p.sA = sA;
   p.B = (const unsigned short*)B; p.ldb = ldb; p.sB = sB;
@@ -543,14 +373,7 @@ static int gemm_run(const void* A, long lda, long sA, int a_kcontig,
   p.alpha = alpha; p.batch = batch; p.ws = ws;
   p.ay = (const unsigned short*)act_y; p.lday = lday; p.bact = bwd_act; p.colsum = colsum; p.rowsum_a = rowsum_a;
   p.n_fast = M >= N;
-  p.uw = upd ? upd->w : nullptr;
-  p.uwc = upd ? upd->wc : nullptr;
-  p.uv = upd ? upd->v : nullptr;
-  p.ulr = upd ? upd->lr : nullptr;
-  p.uwd = upd ? upd->wd : 0.f;
-  p.umom = upd ? upd->mom : 0.f;
-  p.unest = upd ? upd->nest : 0;
-  p.ulds = upd != nullptr;   // the update staged through LDS (whole-row W accesses, gemm.hip sgd_epilogue_lds)
+  gemm_set_update(p, upd);
   // vector (16-B) loads need the contiguous extent and leading dims to be multiples of 8
   auto al = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
   bool vec = al(A) && al(B) && (lda % 8 == 0) && (ldb % 8 == 0) && (sA % 8 == 0) && (sB % 8 == 0);
@@ -574,7 +397,7 @@ static int gemm_run(const void* A, long lda, long sA, int a_kcontig,
   // per GPU): 64x64 tiles give 4x the blocks without split-K slabs (measured +26 % step rate)
   if (t128 < 128 && K <= 2048) { BMv = 64; BNv = 64; }
   // a fused backward epilogue in the tile cannot split K: small grids with a long K split it and run
-  // the epilogue in the reduce (fm_gemm_splitk_reduce_bwd), short ones take 64x64 tiles for 4x the
+  // the epilogue in the reduce (fm_gemm_reduce_bwd), short ones take 64x64 tiles for 4x the
   // blocks (summit_large dX, 256 x 4096 x 4096)
   const bool fused_ep = act_y != nullptr || colsum != nullptr;
   const bool fused_split = fused_ep && t128 < 256 && K >= 1024 && ws != nullptr && batch == 1 && ksplit_req <= 0 &&
@@ -607,18 +430,10 @@ static int gemm_run(const void* A, long lda, long sA, int a_kcontig,
   {   // LDS-DMA staging for full tiles (FM_GEMM_DMA=0: register staging everywhere)
     p.dma = fm_gemm_dma_enabled() && vec && M % BMv == 0 && N % BNv == 0 && K % BK == 0 && K > 0;
   }
-  const bool reduce_bwd = p.ksplit > 1 && fused_ep;
   if (BNv == 128) launch_bm<128, 128>(p, a_kcontig, b_kcontig, vec, stream);
   else if (BMv == 128) launch_bm<128, 64>(p, a_kcontig, b_kcontig, vec, stream);
   else launch_bm<64, 64>(p, a_kcontig, b_kcontig, vec, stream);
-  if (reduce_bwd) {
-    const int bx = (N + 1023) / 1024;
-    const int by = std::max(1, std::min(M, 1024 / bx));
-    const int RB = (M + by - 1) / by;
-    hipLaunchKernelGGL(fm_gemm_splitk_reduce_bwd, dim3(bx, (M + RB - 1) / RB), dim3(256), 0, stream, p, RB);
-  } else if (p.ksplit > 1) {
-    launch_splitk_reduce(p, stream);
-  }
+  if (p.ksplit > 1) launch_splitk_reduce(p, fused_ep, stream);
   return p.ksplit;
 }
 

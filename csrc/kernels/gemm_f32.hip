@@ -18,10 +18,10 @@
 //     INTERLEAVED over its tiles (tile t, lane row q -> row base + T*q + t) so one b128 read at a
 //     fixed k gives the fragments of all T tiles.  No transposed copies, no scalar LDS reads.
 // The epilogue undoes the interleave: each lane owns groups of 4 consecutive output columns
-// (16-B stores).  Fused epilogue like the bf16 kernel (gemm_common.h): alpha, bias[n],
+// (16-B stores).  The epilogue is the bf16 kernel's (gemm_epilogue.h): alpha, bias[n],
 // activation, activation-backward of the layer below (y fp32) + its bias-gradient column sums,
 // beta accumulate; dW GEMMs fold the bias gradient in as row sums of the staged A tiles.
-// Split-K writes fp32 slabs reduced by one vectorised reduce launch.  XCD-aware tile order.
+// Split-K writes fp32 slabs reduced by one reduce launch (gemm_epilogue.h).  XCD-aware tile order.
 #include "gemm_f32_common.h"
 
 #include <algorithm>
@@ -50,10 +50,9 @@ __global__ void __launch_bounds__(NT, MINB) fm_gemm_f32_kernel(GemmF p) {
   const int wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
 
-  const int bid = xcd_remap_f(blockIdx.x, p.tiles_m * p.tiles_n);
-  int tm, tn;
-  if (p.n_fast) { tn = bid % p.tiles_n; tm = bid / p.tiles_n; }
-  else { tm = bid % p.tiles_m; tn = bid / p.tiles_m; }
+  const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+  const TileMN tile = tile_coords(p, bid);
+  const int tm = tile.m, tn = tile.n;
   const int zb = blockIdx.y;
   const int split = blockIdx.z;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -194,153 +193,12 @@ __global__ void __launch_bounds__(NT, MINB) fm_gemm_f32_kernel(GemmF p) {
   }
   if constexpr (SGD) {
     if (p.ksplit == 1 && p.ulds) {
-      sgd_epilogue_lds_f32<BM, BN, NT, MR, NR, !AK, !BKC, 2 * (BM + BN) * BKF * 4>(p, acc, smem, m0, n0, m0 + wm * TM,
-                                                                                   n0 + wn * TN, lane, tid);
+      sgd_epilogue_lds<BM, BN, NT, MR, NR, !AK, !BKC, 2 * (A_BYTES + B_BYTES)>(p, acc, smem, m0, n0, m0 + wm * TM,
+                                                                               n0 + wn * TN, lane, tid);
       return;
     }
   }
-  epilogue_f32<MR, NR, !AK, !BKC, SGD>(p, acc, zb, split, m0 + wm * TM, n0 + wn * TN, lane);
-}
-
-// split-K reduce: 4 consecutive outputs per thread when N % 4 == 0 (16-B slab loads)
-template <bool SGD>
-__global__ void fm_gemm_f32_reduce(GemmF p, int v4) {
-  const long MN = (long)p.M * p.N;
-  const int E = v4 ? 4 : 1;
-  const long total = MN * p.batch / E;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long e0 = i * E;
-    const long zb = e0 / MN, e = e0 % MN;
-    const int m = (int)(e / p.N), n = (int)(e % p.N);
-    const float* src = p.ws + zb * p.ksplit * MN + e;
-    float* d = p.C + zb * p.sC + (long)m * p.ldc + n;
-    if (v4) {
-      f32x4_t s = slab_sum4(src, MN, p.ksplit);
-      if constexpr (SGD) {
-        sgd_apply4(p, (long)m * p.ldc + n, s * p.alpha);
-        continue;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s[r] = act_fwd(p.act, s[r] * p.alpha + (p.bias ? p.bias[n + r] : 0.f));
-      if (p.beta) s += *reinterpret_cast<const f32x4_t*>(d);
-      *reinterpret_cast<f32x4_t*>(d) = s;
-    } else {
-      float s = slab_sum1(src, MN, p.ksplit);
-      if constexpr (SGD) {
-        sgd_apply1(p, (long)m * p.ldc + n, s * p.alpha);
-        continue;
-      }
-      s = act_fwd(p.act, s * p.alpha + (p.bias ? p.bias[n] : 0.f));
-      *d = s + (p.beta ? *d : 0.f);
-    }
-  }
-}
-
-// split-K reduce for DEEP splits (ks >= 16, N % 4 == 0; the small-output dW GEMMs: 128 x 256 x 8192
-// runs 64-way): the one-thread-per-4-outputs reduce above leaves a 32-block grid with 64 dependent
-// slab reads per thread (21 us for 8 MB, profiles/prof_r5final_step_fp32.txt).  Here G = 8 threads
-// share each 4-output group -- thread g sums slabs g, g + 8, ... in order -- and the G partial sums are
-// added through LDS in g order (deterministic): 8x the blocks and the loads in flight.
-constexpr int RD_G = 8;
-template <bool SGD>
-__global__ void __launch_bounds__(256) fm_gemm_f32_reduce_deep(GemmF p) {
-  __shared__ f32x4_t part[RD_G][256 / RD_G];
-  constexpr int O = 256 / RD_G;
-  const long MN = (long)p.M * p.N;
-  const long total = MN * p.batch / 4;
-  const int o = threadIdx.x % O, g = threadIdx.x / O;
-  const long i = blockIdx.x * (long)O + o;
-  const long e0 = (i < total ? i : total - 1) * 4;
-  const long zb = e0 / MN, e = e0 % MN;
-  const float* src = p.ws + zb * p.ksplit * MN + e;
-  f32x4_t s = {0.f, 0.f, 0.f, 0.f};
-  int k = g;
-  for (; k + 3 * RD_G < p.ksplit; k += 4 * RD_G) {
-    f32x4_t v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(src + (long)(k + u * RD_G) * MN);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) s += v[u];
-  }
-  for (; k < p.ksplit; k += RD_G) s += *reinterpret_cast<const f32x4_t*>(src + (long)k * MN);
-  part[g][o] = s;
-  __syncthreads();
-  if (g != 0 || i >= total) return;
-  s = part[0][o];
-#pragma unroll
-  for (int t = 1; t < RD_G; ++t) s += part[t][o];
-  const int m = (int)(e / p.N), n = (int)(e % p.N);
-  if constexpr (SGD) {
-    sgd_apply4(p, (long)m * p.ldc + n, s * p.alpha);
-    return;
-  }
-  float* d = p.C + zb * p.sC + (long)m * p.ldc + n;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) s[r] = act_fwd(p.act, s[r] * p.alpha + (p.bias ? p.bias[n + r] : 0.f));
-  if (p.beta) s += *reinterpret_cast<const f32x4_t*>(d);
-  *reinterpret_cast<f32x4_t*>(d) = s;
-}
-
-// split-K reduce of a GEMM with the FUSED BACKWARD epilogue (dX of a layer whose input has an
-// activation): v = act_bwd(bact, ay, act(alpha * sum + bias)), colsum[n] += sum over rows of v.
-// Thread = 4 columns x RB rows: the column sums stay in registers, one atomic per (column, block),
-// so small-batch dX GEMMs (summit_large: 256 x 4096 x 4096) can split K instead of running 64
-// blocks of 128x128 tiles or 64x64 tiles at ~60 % of the big-tile rate.
-__global__ void __launch_bounds__(256) fm_gemm_f32_reduce_bwd(GemmF p, int RB) {
-  const int n = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (n >= p.N) return;
-  const int m0 = blockIdx.y * RB, m1 = min(p.M, m0 + RB);
-  const long MN = (long)p.M * p.N;
-  const bool v4 = n + 3 < p.N && (p.N & 3) == 0;
-  float cs[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int m = m0; m < m1; ++m) {
-    const float* src = p.ws + (long)m * p.N + n;
-    float sv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (v4) {
-      f32x4_t a = slab_sum4(src, MN, p.ksplit);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sv[r] = a[r];
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (n + r < p.N)
-          sv[r] = slab_sum1(src + r, MN, p.ksplit);
-    }
-    float* d = p.C + (long)m * p.ldc + n;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (n + r >= p.N) break;
-      float v = act_fwd(p.act, sv[r] * p.alpha + (p.bias ? p.bias[n + r] : 0.f));
-      if (p.ay) v = act_bwd(p.bact, p.ay[(long)m * p.lday + n + r], v);
-      cs[r] += v;
-      d[r] = v + (p.beta ? d[r] : 0.f);
-    }
-  }
-  if (p.colsum) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (n + r < p.N) atomicAdd(p.colsum + n + r, cs[r]);
-  }
-}
-
-}  // namespace
-
-// the split-bf16 kernel, second form (gemm_x3.hip)
-extern "C" int fm_gemm_x3v2_launch(const void* params, int bm, int bn, int a_kcontig, int b_kcontig, int sgd,
-                                   hipStream_t s);
-
-
-namespace {
-
-void launch_reduce_f32(const GemmF& p, int v4, long total, hipStream_t stream) {
-  if (v4 && p.ksplit >= 16) {
-    const dim3 grid((unsigned)((total + 256 / RD_G - 1) / (256 / RD_G)));
-    if (p.uw) hipLaunchKernelGGL(fm_gemm_f32_reduce_deep<true>, grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(fm_gemm_f32_reduce_deep<false>, grid, dim3(256), 0, stream, p);
-    return;
-  }
-  if (p.uw) hipLaunchKernelGGL(fm_gemm_f32_reduce<true>, dim3(fm_grid(total)), dim3(256), 0, stream, p, v4);
-  else hipLaunchKernelGGL(fm_gemm_f32_reduce<false>, dim3(fm_grid(total)), dim3(256), 0, stream, p, v4);
+  gemm_epilogue<MR, NR, !AK, !BKC, SGD>(p, acc, zb, split, m0 + wm * TM, n0 + wn * TN, lane);
 }
 
 template <int BM, int BN, bool AK, bool BKC, bool VEC>
@@ -512,14 +370,10 @@ extern "C" int fm_gemm_f32_get_split() { return f32_split_mode(); }
 static thread_local int g_last_form = 0;
 extern "C" int fm_gemm_f32_last_form() { return g_last_form; }
 
-struct SgdUpdF {
-  float* w; unsigned short* wc; float* v; const float* lr; float wd, mom; int nest;
-};
-
 static int gemm_f32_run(const float* A, long lda, long sA, int a_kcontig, const float* B, long ldb, long sB,
                         int b_kcontig, float* C, long ldc, long sC, const float* bias, int M, int N, int K, int batch,
                         float alpha, int beta, int act, float* ws, long ws_bytes, int ksplit_req, const float* act_y,
-                        long lday, int bwd_act, float* colsum, float* rowsum_a, const SgdUpdF* upd,
+                        long lday, int bwd_act, float* colsum, float* rowsum_a, const SgdUpd* upd,
                         hipStream_t stream);
 
 extern "C" int fm_gemm_f32(const float* A, long lda, long sA, int a_kcontig, const float* B, long ldb, long sB,
@@ -538,7 +392,7 @@ extern "C" int fm_gemm_f32_dw_sgd(const float* A, long lda, const float* B, long
                                   unsigned short* Wc, float* V, const float* lr, float wd, float mom, int nesterov,
                                   int M, int N, int K, float* ws, long ws_bytes, float* rowsum_a, int cfg,
                                   hipStream_t stream) {
-  SgdUpdF u{W, Wc, V, lr, wd, mom, nesterov};
+  SgdUpd u{W, Wc, V, lr, wd, mom, nesterov};
   return gemm_f32_run(A, lda, 0, 0, B, ldb, 0, 0, W, ldw, 0, nullptr, M, N, K, 1, 1.f, 0, 10, ws, ws_bytes, cfg, nullptr,
                       0, 10, nullptr, rowsum_a, &u, stream);
 }
@@ -546,12 +400,10 @@ extern "C" int fm_gemm_f32_dw_sgd(const float* A, long lda, const float* B, long
 static int gemm_f32_run(const float* A, long lda, long sA, int a_kcontig, const float* B, long ldb, long sB,
                         int b_kcontig, float* C, long ldc, long sC, const float* bias, int M, int N, int K, int batch,
                         float alpha, int beta, int act, float* ws, long ws_bytes, int ksplit_req, const float* act_y,
-                        long lday, int bwd_act, float* colsum, float* rowsum_a, const SgdUpdF* upd,
+                        long lday, int bwd_act, float* colsum, float* rowsum_a, const SgdUpd* upd,
                         hipStream_t stream) {
   if (M <= 0 || N <= 0 || batch <= 0) return 0;
-  if (upd && (K <= 0 || ldc % 4 != 0 || (((uintptr_t)upd->w | (uintptr_t)(upd->v ? upd->v : upd->w)) & 15) ||
-              (((uintptr_t)(upd->wc ? (void*)upd->wc : (void*)upd->w)) & 7)))
-    return -1;
+  if (upd && !sgd_upd_ok(*upd, K, ldc)) return -1;
   GemmF p;
   p.A = A; p.lda = lda; p.sA = sA;
   p.B = B; p.ldb = ldb; p.sB = sB;
@@ -559,14 +411,7 @@ static int gemm_f32_run(const float* A, long lda, long sA, int a_kcontig, const 
   p.bias = bias; p.ws = ws; p.ay = act_y; p.lday = lday; p.colsum = colsum; p.rowsum_a = rowsum_a;
   p.bact = bwd_act; p.M = M; p.N = N; p.K = K; p.act = act; p.beta = beta; p.batch = batch; p.alpha = alpha;
   p.n_fast = M >= N;
-  p.uw = upd ? upd->w : nullptr;
-  p.uwc = upd ? upd->wc : nullptr;
-  p.uv = upd ? upd->v : nullptr;
-  p.ulr = upd ? upd->lr : nullptr;
-  p.uwd = upd ? upd->wd : 0.f;
-  p.umom = upd ? upd->mom : 0.f;
-  p.unest = upd ? upd->nest : 0;
-  p.ulds = upd != nullptr;   // the update staged through LDS (whole-row W accesses)
+  gemm_set_update(p, upd);
   p.dma = 0;
   p.amax_a = p.amax_b = nullptr;
   p.amax_na = p.amax_nb = 1;
@@ -638,11 +483,7 @@ static int gemm_f32_run(const float* A, long lda, long sA, int a_kcontig, const 
       }
       g_last_form = bm == 256 ? 4 : bn == 64 ? 6 : 5;
       if (fm_gemm_x3v2_launch(&p, bm, bn, a_kcontig, b_kcontig, upd != nullptr && ks == 1, stream) == 0) {
-        if (ks > 1) {
-          const int v4 = (N % 4 == 0) && (ldc % 4 == 0) && (sC % 4 == 0) && al(C);
-          const long total = (long)M * N * batch / (v4 ? 4 : 1);
-          launch_reduce_f32(p, v4, total, stream);
-        }
+        if (ks > 1) launch_splitk_reduce(p, false, stream);   // fused: ks == 1
         return ks;
       }
     }
@@ -658,7 +499,7 @@ static int gemm_f32_run(const float* A, long lda, long sA, int a_kcontig, const 
   // small grids take 64x64 tiles for 4x the blocks (summit_large dX, 256 x 4096 x 4096: 64 -> 256
   // blocks on 256 CUs)
   // ... unless K is long enough to split it: then 128x128 tiles split K and the fused epilogue runs in
-  // the reduce (fm_gemm_f32_reduce_bwd)
+  // the reduce (fm_gemm_reduce_bwd)
   const bool fused_ep = act_y != nullptr || colsum != nullptr;
   const bool fused_split = fused_ep && t128 < 256 && K >= 1024 && ws != nullptr && batch == 1 && ksplit_req <= 0 &&
                            (long)M * N * 4 * 2 <= ws_bytes;
@@ -693,16 +534,7 @@ static int gemm_f32_run(const float* A, long lda, long sA, int a_kcontig, const 
   if (BNv == 128) launch_fbm<128, 128>(p, a_kcontig, b_kcontig, vec, stream);
   else if (BMv == 128) launch_fbm<128, 64>(p, a_kcontig, b_kcontig, vec, stream);
   else launch_fbm<64, 64>(p, a_kcontig, b_kcontig, vec, stream);
-  if (ks > 1 && fused_ep) {
-    const int bx = (N + 1023) / 1024;
-    const int by = std::max(1, std::min(M, 1024 / bx));
-    const int RB = (M + by - 1) / by;
-    hipLaunchKernelGGL(fm_gemm_f32_reduce_bwd, dim3(bx, (M + RB - 1) / RB), dim3(256), 0, stream, p, RB);
-  } else if (ks > 1) {
-    const int v4 = (N % 4 == 0) && (ldc % 4 == 0) && (sC % 4 == 0) && al(C);
-    const long total = (long)M * N * batch / (v4 ? 4 : 1);
-    launch_reduce_f32(p, v4, total, stream);
-  }
+  if (ks > 1) launch_splitk_reduce(p, fused_ep, stream);
   return ks;
 }
 

@@ -20,7 +20,7 @@
 //     fence would drain every DMA in flight);
 //   * the MFMA operands are swapped (B fragment as the MFMA "A"), so each lane ends up owning 4
 //     consecutive output columns: acc[i][j][r] = C[mb + 16 i + (lane & 15)][nb + 16 j + 4 (lane >> 4) + r]
-//     -- the layout every flexmi GEMM epilogue takes (gemm_common.h, gemm_f32_common.h).
+//     -- the layout every flexmi GEMM epilogue takes (gemm_epilogue.h).
 // Full tiles only: the host guarantees M % BM == 0, N % BN == 0, (K per split) % BK == 0, 16-B aligned
 // rows (ld % 8 == 0 elements) and plane strides.
 #pragma once
@@ -28,9 +28,6 @@
 
 namespace {
 namespace mp {
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 template <int N>
 FM_DEVICE void wait_vm() {

@@ -31,7 +31,7 @@
 // Tiles: 256x128 (8 waves, 144 KiB LDS) or 128x128 (4 waves, 96 KiB), one block per CU, or 128x64
 // (2 waves, 72 KiB, two blocks per CU),
 // XCD-aware tile order, split-K slabs / fused epilogues / fused SGD shared with the native kernel
-// (gemm_f32_common.h epilogue_f32).
+// (gemm_epilogue.h).
 #include "gemm_f32_common.h"
 
 #include <cstdlib>
@@ -196,15 +196,9 @@ __global__ void __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) fm_gemm_x3v2_ke
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int bid = xcd_remap_f(blockIdx.x, p.tiles_m * p.tiles_n);
-  int tm, tn;
-  if (p.n_fast) {
-    tn = bid % p.tiles_n;
-    tm = bid / p.tiles_n;
-  } else {
-    tm = bid % p.tiles_m;
-    tn = bid / p.tiles_m;
-  }
+  const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+  const TileMN tile = tile_coords(p, bid);
+  const int tm = tile.m, tn = tile.n;
   const int zb = blockIdx.y, split = blockIdx.z;
   const int m0 = tm * BM, n0 = tn * BN;
   const float* A = p.A + (long)zb * p.sA;
@@ -378,7 +372,7 @@ __global__ void __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) fm_gemm_x3v2_ke
       }
     }
   }
-  epilogue_f32<MR, NR, false, false, SGD>(p, acc, zb, split, m0 + wm * 64, n0 + wn * 64, lane);
+  gemm_epilogue<MR, NR, false, false, SGD>(p, acc, zb, split, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
 template <int BM, int BN, bool SGD, int SCHED, bool F16 = false>
@@ -433,9 +427,9 @@ void launch_x3v2(const GemmF& p, bool ak, bool bk, hipStream_t s) {
 // sgd: the fused-SGD epilogue (unsplit tiles only).  Returns -1 for an unsupported tile.
 // bn = 128, or 64 with bm = 128: the 128x64 tile (2 waves, 72 KiB LDS, two blocks per CU) for the
 // narrow layers (N = 256 / 512 at batch 8192: 256 / 512 tiles where 128x128 gives half a wave)
-extern "C" int fm_gemm_x3v2_launch(const void* params, int bm, int bn, int a_kcontig, int b_kcontig, int sgd,
+extern "C" int fm_gemm_x3v2_launch(const GemmF* params, int bm, int bn, int a_kcontig, int b_kcontig, int sgd,
                                    hipStream_t s) {
-  const GemmF& p = *static_cast<const GemmF*>(params);
+  const GemmF& p = *params;
   if (sgd && p.ksplit > 1) return -1;
   if (bm == 256 && bn == 128) {
     if (sgd) launch_x3v2<256, 128, true>(p, a_kcontig, b_kcontig, s);

@@ -1,7 +1,7 @@
 // The dense update rules (SGD, Adagrad, Adam) and the one traversal that applies a rule to a range
 // of a rank's flat fp32 buffers.  This is the only place in csrc/kernels/ where a rule's
 // arithmetic is written: the optimizer launches (optim.hip), the fused dW-SGD GEMM epilogues
-// (gemm_common.h sgd_apply1 / sgd_apply4) and the small-K reduce (gemm_small.hip) all call it, so
+// (gemm_epilogue.h sgd_apply1 / sgd_apply4) and the small-K reduce (gemm_small.hip) all call it, so
 // scalar head, 16-B body, scalar tail and every fused form compute the same values.
 #pragma once
 #include "common.h"

@@ -48,16 +48,22 @@ def test_gemm_f32_epilogue_bias_act_beta(gpu):
         assert rel_err(C, ref) < TOL, act
 
 
-@pytest.mark.parametrize("ks", [2, 4, 8, 16, 64])      # >= 16: the slab-parallel reduce
-def test_gemm_f32_splitk_and_batch(gpu, ks):
+# ks >= 16: the slab-parallel reduce; ragged: the scalar reduce (N % 4 != 0, a last quad that crosses N, rows
+# past M in the last tile) with bias and beta
+@pytest.mark.parametrize("ks,shape,beta", [(2, (256, 128, 8192), False), (4, (256, 128, 8192), False),
+                                           (8, (256, 128, 8192), False), (16, (256, 128, 8192), False),
+                                           (64, (256, 128, 8192), False), (4, (77, 130, 2048), True)],
+                         ids=["2", "4", "8", "16", "64", "4-ragged"])
+def test_gemm_f32_splitk_and_batch(gpu, ks, shape, beta):
     from flexmi.ops import _kernels as Kk
     torch.manual_seed(2)
-    M, N, K = 256, 128, 8192
+    M, N, K = shape
     A, B = torch.randn(K, M, device=gpu), torch.randn(K, N, device=gpu)
     bias = torch.randn(N, device=gpu)
-    C = torch.empty(M, N, device=gpu)
-    assert Kk.gemm(A, M, False, B, N, False, C, N, M, N, K, bias=bias, ksplit=ks) == ks
-    assert rel_err(C, A.double().t() @ B.double() + bias.double()) < TOL
+    C = torch.randn(M, N, device=gpu)
+    C0 = C.double().clone()
+    assert Kk.gemm(A, M, False, B, N, False, C, N, M, N, K, bias=bias, beta=beta, ksplit=ks) == ks
+    assert rel_err(C, A.double().t() @ B.double() + bias.double() + (C0 if beta else 0)) < TOL
     bs = 5
     X, Y = torch.randn(bs, 40, 72, device=gpu), torch.randn(bs, 72, 24, device=gpu)
     O = torch.empty(bs, 40, 24, device=gpu)
@@ -503,23 +509,27 @@ def test_dlrm_hdf5_dataset_fp32_gpu_matches_cpu(gpu, tmp_path):
     _assert_params_close(res["cpu"], res["gpu"], 1e-4)
 
 
-@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_fused_backward_epilogue_split_k_small_batch(gpu, dtype):
+# dX [M, K] = dpre [M, N] . W [N, K]: split (the epilogue in the reduce), with an output width that is
+# no multiple of 4, and the unsplit partner at a partial tile (the same rule in the tile epilogue)
+@pytest.mark.parametrize("dtype,M,K,N,split", [("fp32", 256, 2048, 4096, True), ("bf16", 256, 2048, 4096, True),
+                                               ("fp32", 256, 130, 4096, True), ("bf16", 256, 130, 4096, True),
+                                               ("fp32", 100, 136, 256, False), ("bf16", 100, 136, 256, False)],
+                         ids=["fp32", "bf16", "fp32-w130", "bf16-w130", "fp32-unsplit", "bf16-unsplit"])
+def test_fused_backward_epilogue_split_k_small_batch(gpu, dtype, M, K, N, split):
     """Small-batch dX GEMM with the fused backward epilogue (summit_large: 256 x 4096 x 4096): the
     grid is small, so K is split and the act-bwd + bias-gradient column sums run in the split-K
-    reduce (fm_gemm_f32_reduce_bwd / fm_gemm_splitk_reduce_bwd) -- same results as the oracle."""
+    reduce (fm_gemm_reduce_bwd) -- same results as the oracle."""
     from flexmi.ops import _kernels as Kk
     torch.manual_seed(9)
     dt = torch.float32 if dtype == "fp32" else torch.bfloat16
     tol = TOL if dtype == "fp32" else 2e-2
-    M, K, N = 256, 2048, 4096          # dpre [M, N] . W [N, K] -> dX [M, K]
     dpre = torch.randn(M, N, device=gpu).to(dt)
     W = (torch.randn(N, K, device=gpu) * 0.05).to(dt)
     yb = torch.randn(M, K, device=gpu).relu().to(dt)
     dx = torch.empty(M, K, device=gpu, dtype=dt)
     colsum = torch.zeros(K, device=gpu)
     ks = Kk.gemm(dpre, N, True, W, K, False, dx, K, M, K, N, act_y=yb, bwd_act=11, colsum=colsum)
-    assert ks > 1
+    assert ks > 1 if split else ks == 1
     ref = (dpre.double() @ W.double()) * (yb.double() > 0)
     assert rel_err(dx, ref) < tol
     assert rel_err(colsum, ref.sum(0)) < tol

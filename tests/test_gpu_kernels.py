@@ -49,15 +49,30 @@ def test_gemm_epilogue_bias_relu_bf16_beta(gpu):
 
 
 def test_gemm_splitk_and_batch(gpu):
+    """Split-K slabs and their reduce: fp32 C takes the 16-B reduce, bf16 C the scalar one with a bf16
+    store; bias + ReLU + beta run in the reduce; 77 x 130 has N % 4 != 0, a last quad that crosses N
+    and rows past M in the last tile.  Oracle: float64 on the same bf16 operands."""
     from flexmi.ops import _kernels as Kk
     torch.manual_seed(2)
-    M, N, K = 64, 128, 4096
-    A, B = torch.randn(K, M, device=gpu), torch.randn(K, N, device=gpu)
-    C = torch.empty(M, N, device=gpu)
-    ks = Kk.gemm(bf(A), M, False, bf(B), N, False, C, N, M, N, K, ksplit=8)
-    assert ks == 8
-    ref = bf(A).float().t() @ bf(B).float()
-    assert rel_err(C, ref) < 2e-3
+    bad = []
+    for M, N, K, ks, c_dt, epi in [(64, 128, 4096, 8, torch.float32, False), (64, 128, 4096, 8, torch.bfloat16, False),
+                                   (64, 128, 4096, 8, torch.float32, True), (64, 128, 4096, 8, torch.bfloat16, True),
+                                   (77, 130, 2048, 4, torch.float32, False), (77, 130, 2048, 4, torch.float32, True),
+                                   (77, 130, 2048, 4, torch.bfloat16, True)]:
+        A, B = bf(torch.randn(K, M, device=gpu)), bf(torch.randn(K, N, device=gpu))
+        bias = torch.randn(N, device=gpu)
+        C = torch.randn(M, N, device=gpu).to(c_dt)
+        C0 = C.double().clone()
+        ref = A.double().t() @ B.double()
+        if epi:
+            got = Kk.gemm(A, M, False, B, N, False, C, N, M, N, K, bias=bias, act=11, beta=True, ksplit=ks)
+            ref = torch.relu(ref + bias.double()) + C0
+        else:
+            got = Kk.gemm(A, M, False, B, N, False, C, N, M, N, K, ksplit=ks)
+        err = rel_err(C, ref.float())
+        if got != ks or not err < (2e-3 if c_dt == torch.float32 else 1e-2):
+            bad.append((M, N, K, ks, c_dt, epi, got, err))
+    assert not bad, bad           # every failing case, not the first
     # batched
     bs = 5
     X, Y = torch.randn(bs, 40, 72, device=gpu), torch.randn(bs, 72, 24, device=gpu)
