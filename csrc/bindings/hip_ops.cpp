@@ -126,6 +126,7 @@ void fm_pool_fwd(const void* x, void* y, unsigned char* code, int N, int C, int 
 void fm_pool_bwd(const void* x, const void* y, const void* dy, void* dx, unsigned char* code, int code_ready, int N, int C,
                  int H, int W, int P, int Q, int kh, int kw, int sh, int sw, int pt, int pl, int is_max, int act, int acc,
                  int bf16, hipStream_t st);
+void fm_pool_last_form(int* out);
 void fm_bn_fwd(const void* x, void* y, const float* gamma, const float* beta, float* stats, float* meaninv, int N, int C,
                int HW, float eps, int relu, int bf16, hipStream_t st);
 void fm_bn_bwd(const void* x, const void* y, const void* dy, const float* meaninv, const float* gamma, float* gsum,
@@ -966,6 +967,16 @@ void multi_copy(std::vector<torch::Tensor> src, std::vector<int64_t> src_off, st
                 std::vector<int64_t> dst_off, std::vector<int64_t> rows, std::vector<int64_t> cols, std::vector<int64_t> lds,
                 std::vector<int64_t> ldd, int64_t add_mask) {
   int n = (int)src.size();
+  // add_mask carries one accumulate bit per piece of ONE launch table (32): a call with more pieces
+  // may only copy (flexmi/ops/_kernels.py _multi_copy splits accumulating lists into calls of <= 32)
+  TORCH_CHECK(add_mask >= 0 && (add_mask >> 32) == 0 && (n >= 32 || (add_mask >> n) == 0),
+              "multi_copy: add_mask ", add_mask, " names a piece beyond the ", n, " given (32 mask bits)");
+  TORCH_CHECK(n <= 32 || add_mask == 0, "multi_copy: ", n,
+              " pieces with accumulate flags; the mask carries 32 -- split the call");
+  TORCH_CHECK(dst.size() == src.size() && src_off.size() == src.size() && dst_off.size() == src.size() &&
+                  rows.size() == src.size() && cols.size() == src.size() && lds.size() == src.size() &&
+                  ldd.size() == src.size(),
+              "multi_copy: one entry per piece in every list");
   std::vector<const void*> s(n);
   std::vector<void*> d(n);
   std::vector<long> r(n), c(n), a(n), b(n);
@@ -1567,6 +1578,18 @@ PYBIND11_MODULE(_C, m) {
   m.def("transpose_batched", &transpose_batched);
   m.def("pool_fwd", &pool_fwd);
   m.def("pool_bwd", &pool_bwd);
+  // the kernels this thread's last pool_fwd / pool_bwd ran: {"fwd": (form, nbands, G), "bwd": (form, nbands, G)}
+  // with form "planes" (several planes per block) / "band" / "per_output" and "scatter" / "band" / "rows"
+  m.def("pool_last_form", []() {
+    int f[6];
+    fm_pool_last_form(f);
+    static const char* const fw[] = {"none", "planes", "band", "per_output"};
+    static const char* const bw[] = {"none", "scatter", "band", "rows"};
+    py::dict d;
+    d["fwd"] = py::make_tuple(fw[f[0]], f[1], f[2]);
+    d["bwd"] = py::make_tuple(bw[f[3]], f[4], f[5]);
+    return d;
+  });
   m.def("bn_fwd", &bn_fwd);
   m.def("bn_bwd", &bn_bwd);
   m.def("compact_rows", &compact_rows);

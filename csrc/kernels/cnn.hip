@@ -608,16 +608,21 @@ __global__ void __launch_bounds__(256) fm_strided_copy4(const T* __restrict__ sr
 }
 
 // ---- batch norm (training mode, per-channel statistics over N*H*W) -----------------------
-// stats[0:C] = sum, stats[C:2C] = sum of squares   (zeroed by the caller)
+// stats[0:C] = sum of (x - pivot), stats[C:2C] = sum of (x - pivot)^2   (zeroed by the caller), with
+// pivot = the channel's first element: the one-pass variance E[d^2] - E[d]^2 then cancels digits in
+// proportion to (mean - pivot)^2 / var, about 1, instead of mean^2 / var (1e4 for activations at
+// mean / std = 100: fp32 output error 3.9e-4 of the largest output on a (4, 3, 24, 24) input without
+// the pivot, 6.8e-7 with it; tests/test_gpu_pool_bn_forms.py test_batchnorm_offset_inputs)
 template <typename T>
 __global__ void __launch_bounds__(256) fm_bn_stats_kernel(const T* __restrict__ x, float* __restrict__ stats,
                                                           int N, int C, int HW) {
   const int c = blockIdx.y;
   float s = 0.f, s2 = 0.f;
   const long per_c = (long)N * HW;
+  const float pivot = per_c > 0 ? tof(x[(long)c * HW]) : 0.f;
   for (long j = blockIdx.x * (long)blockDim.x + threadIdx.x; j < per_c; j += (long)gridDim.x * blockDim.x) {
     const long n = j / HW, hw = j % HW;
-    const float v = tof(x[(n * C + c) * HW + hw]);
+    const float v = tof(x[(n * C + c) * HW + hw]) - pivot;
     s += v;
     s2 += v * v;
   }
@@ -645,13 +650,14 @@ __global__ void __launch_bounds__(256) fm_bn_apply_kernel(const T* __restrict__ 
   const float m = (float)N * HW;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)((i / HW) % C);
-    const float mean = stats[c] / m;
-    const float var = fmaxf(stats[C + c] / m - mean * mean, 0.f);
+    const float d = stats[c] / m;                      // mean - pivot (see fm_bn_stats_kernel)
+    const float mean = tof(x[(long)c * HW]) + d;
+    const float var = fmaxf(stats[C + c] / m - d * d, 0.f);
     const float inv = rsqrtf(var + eps);
     if (i < C) {   // one thread per channel records the statistics
-      const float mc = stats[i] / m;
-      meaninv[i] = mc;
-      meaninv[C + i] = rsqrtf(fmaxf(stats[C + i] / m - mc * mc, 0.f) + eps);
+      const float dc = stats[i] / m;
+      meaninv[i] = tof(x[i * HW]) + dc;
+      meaninv[C + i] = rsqrtf(fmaxf(stats[C + i] / m - dc * dc, 0.f) + eps);
     }
     float v = (tof(x[i]) - mean) * inv * gamma[c] + beta[c];
     if (relu) v = fmaxf(v, 0.f);
@@ -767,6 +773,15 @@ static void fm_transpose_batched_t(const void* in, const void* yin, void* out, i
 // the 16-B staged bf16 forward (fm_pool_fwd_band_v8) for bf16; the 2-B staging band kernel for fp32
 constexpr bool POOL_FWD_V8 = true;
 
+// which kernel this thread's last pooling forward / backward dispatched to (fm_pool_last_form: tests
+// assert the path they claim to cover).  Forward: 1 multi-plane band (G > 1), 2 band, 3 per-output;
+// backward: 1 max scatter, 2 band gather, 3 row segments; 0 = none yet.  nbands / G as launched
+// (the per-output and row-segment kernels have neither: 0).
+struct PoolForm {
+  int form, nbands, G;
+};
+static thread_local PoolForm g_pool_fwd_form = {0, 0, 0}, g_pool_bwd_form = {0, 0, 0};
+
 template <typename T>
 static void fm_pool_fwd_t(const void* x, void* y, unsigned char* code, int N, int C, int H, int W, int P, int Q, int kh, int kw,
                           int sh, int sw, int pt, int pl, int is_max, int act, hipStream_t st) {
@@ -780,6 +795,7 @@ static void fm_pool_fwd_t(const void* x, void* y, unsigned char* code, int N, in
     const int G = (nbands == 1 && (long)H * W <= 2048) ? std::max(1, std::min(NC, 4096 / (H * W))) : 1;
     const int rows = G > 1 ? H : std::min(H, (PB - 1) * sh + kh);
     const int blocks = G > 1 ? (NC + G - 1) / G : NC * nbands;
+    g_pool_fwd_form = {G > 1 ? 1 : 2, nbands, G};
     if constexpr (sizeof(T) == 2) {
       if (POOL_FWD_V8) {
         const size_t lds = ((size_t)G * rows * W + 16) * 2;
@@ -794,6 +810,7 @@ static void fm_pool_fwd_t(const void* x, void* y, unsigned char* code, int N, in
                        make_fastdiv(Q), make_fastdiv(P * Q));
     return;
   }
+  g_pool_fwd_form = {3, 0, 0};
   hipLaunchKernelGGL(fm_pool_fwd_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, st, (const T*)x, (T*)y,
                      is_max ? code : nullptr, total, make_fastdiv(Q), make_fastdiv(P), H, W, P, Q, kh, kw, sh, sw, pt, pl,
                      is_max, act);
@@ -821,6 +838,7 @@ static void fm_pool_bwd_t(const void* x, const void* y, const void* dy, void* dx
     if (is_max) {                        // max pooling: scatter through the recorded argmax
       const int blocks = G > 1 ? (NC + G - 1) / G : NC * nbands;
       const size_t lds_s = (size_t)(G > 1 ? G * H : HB) * W * sizeof(float);
+      g_pool_bwd_form = {1, nbands, G};
       hipLaunchKernelGGL(fm_pool_bwd_max_scatter<T>, dim3(blocks), dim3(256), lds_s, st, (const T*)y, (const T*)dy,
                          (const unsigned char*)code, (T*)dx, NC, H, W, P, Q, kh, kw, sh, pt, pl, sw, act, acc, HB, nbands, G,
                          make_fastdiv(Q), make_fastdiv(P * Q), make_fastdiv(kw), make_fastdiv(sh));
@@ -828,6 +846,7 @@ static void fm_pool_bwd_t(const void* x, const void* y, const void* dy, void* dx
     }
     if (lds <= 48 * 1024) {
       const int blocks = G > 1 ? (NC + G - 1) / G : NC * nbands;
+      g_pool_bwd_form = {2, nbands, G};
       hipLaunchKernelGGL(fm_pool_bwd_band<T>, dim3(blocks), dim3(256), lds, st, (const T*)y, (const T*)dy,
                          (const unsigned char*)code, (T*)dx, NC, H, W, P, Q, kh, kw, sh, sw, pt, pl, is_max, act, acc, HB,
                          nbands, maxprows, G, make_fastdiv(W), make_fastdiv(Q), make_fastdiv(sh), make_fastdiv(sw),
@@ -839,6 +858,7 @@ static void fm_pool_bwd_t(const void* x, const void* y, const void* dy, void* dx
     constexpr int VW = 8;
     const int WS = (W + VW - 1) / VW;
     const int rows_total = N * C * H * WS;
+    g_pool_bwd_form = {3, 0, 0};
     hipLaunchKernelGGL((fm_pool_bwd_rows<T, VW>), dim3((rows_total + 255) / 256), dim3(256), 0, st, (const T*)y,
                        (const T*)dy, (const unsigned char*)code, (T*)dx, rows_total, make_fastdiv(WS), make_fastdiv(H),
                        make_fastdiv(sh), make_fastdiv(sw), WS, H, W, P, Q, kh, kw, sh, sw, pt, pl, is_max, act, acc);
@@ -913,6 +933,11 @@ void fm_pool_fwd(const void* x, void* y, unsigned char* code, int N, int C, int 
 void fm_pool_bwd(const void* x, const void* y, const void* dy, void* dx, unsigned char* code, int code_ready, int N, int C, int H, int W, int P, int Q, int kh, int kw, int sh, int sw, int pt, int pl, int is_max, int act, int acc, int bf16, hipStream_t st) {
   if (bf16) fm_pool_bwd_t<unsigned short>(x, y, dy, dx, code, code_ready, N, C, H, W, P, Q, kh, kw, sh, sw, pt, pl, is_max, act, acc, st);
   else fm_pool_bwd_t<float>(x, y, dy, dx, code, code_ready, N, C, H, W, P, Q, kh, kw, sh, sw, pt, pl, is_max, act, acc, st);
+}
+// out[0:3] = the last forward's (form, nbands, G), out[3:6] = the last backward's (see PoolForm)
+void fm_pool_last_form(int* out) {
+  out[0] = g_pool_fwd_form.form; out[1] = g_pool_fwd_form.nbands; out[2] = g_pool_fwd_form.G;
+  out[3] = g_pool_bwd_form.form; out[4] = g_pool_bwd_form.nbands; out[5] = g_pool_bwd_form.G;
 }
 void fm_bn_fwd(const void* x, void* y, const float* gamma, const float* beta, float* stats, float* meaninv, int N, int C, int HW, float eps, int relu, int bf16, hipStream_t st) {
   if (bf16) fm_bn_fwd_t<unsigned short>(x, y, gamma, beta, stats, meaninv, N, C, HW, eps, relu, st);

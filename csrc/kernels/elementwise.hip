@@ -482,6 +482,8 @@ extern "C" void fm_multi_copy2d(int n, const void* const* src, void* const* dst,
       maxe = std::max(maxe, rows[base + i] * cols[base + i] / (vec ? E : 1));
     }
     t.n = m;
+    // add_mask carries the first table's flags only: a caller with more than MAXC accumulating
+    // pieces splits them over calls (the binding refuses, flexmi/ops/_kernels.py _multi_copy splits)
     t.add = base < 32 ? ((unsigned)add_mask >> base) & (m >= 32 ? 0xffffffffu : ((1u << m) - 1u)) : 0u;
     dim3 grid(fm_grid(maxe, 256, 1024), m);
     if (elem_bytes == 2) hipLaunchKernelGGL((fm_multi_copy<unsigned short>), grid, dim3(256), 0, s, t);

@@ -385,78 +385,84 @@ def _outer_inner(shape, axis):
     return outer, inner
 
 
+MULTI_COPY_MAX = 32     # pieces per multi_copy call: one bit of its accumulate mask each
+
+
+def _multi_copy(pieces, adds):
+    """Run the 2-D copies ``pieces`` = [(src, src_off, dst, dst_off, rows, cols, lds, ldd)] on
+    fm_multi_copy; ``adds[i]``: piece i accumulates into its destination.  The one place that turns
+    per-piece booleans into the kernel's bit mask: calls of at most MULTI_COPY_MAX pieces, each with the
+    mask of its own pieces (bit j = the call's j-th piece)."""
+    assert len(pieces) == len(adds)
+    for b in range(0, len(pieces), MULTI_COPY_MAX):
+        ch = pieces[b:b + MULTI_COPY_MAX]
+        mask = 0
+        for j, a in enumerate(adds[b:b + MULTI_COPY_MAX]):
+            if a:
+                mask |= 1 << j
+        C().multi_copy(*[[p[f] for p in ch] for f in range(8)], mask)
+
+
 def concat_forward(inputs, y, axis):
     outer, tot = _outer_inner(y.shape, axis)
-    src, so, dst, do, rows, cols, lds, ldd = [], [], [], [], [], [], [], []
+    pieces = []
     off = 0
     for x in inputs:
         _, inner = _outer_inner(x.shape, axis)
-        src.append(x); so.append(0); dst.append(y); do.append(off)
-        rows.append(outer); cols.append(inner); lds.append(inner); ldd.append(tot)
+        pieces.append((x, 0, y, off, outer, inner, inner, tot))
         off += inner
-    C().multi_copy(src, so, dst, do, rows, cols, lds, ldd, 0)
+    _multi_copy(pieces, [False] * len(pieces))
 
 
 def concat_backward(dy, in_grads, accs, axis, in_shapes=None):
     """in_shapes: shapes of the concatenated inputs -- an input without a gradient (e.g. a model
     input) still occupies its slice of dy, so later slices start after it."""
     outer, tot = _outer_inner(dy.shape, axis)
-    src, so, dst, do, rows, cols, lds, ldd = [], [], [], [], [], [], [], []
-    mask = 0
+    pieces, adds = [], []
     off = 0
-    k = 0
     for i, (g, a) in enumerate(zip(in_grads, accs)):
         if g is None:
             assert in_shapes is not None, "concat_backward: input shapes needed to skip a gradient-less input"
             off += _outer_inner(in_shapes[i], axis)[1]
             continue
         _, inner = _outer_inner(g.shape, axis)
-        src.append(dy); so.append(off); dst.append(g); do.append(0)
-        rows.append(outer); cols.append(inner); lds.append(tot); ldd.append(inner)
-        if a:
-            mask |= 1 << k
-        k += 1
+        pieces.append((dy, off, g, 0, outer, inner, tot, inner))
+        adds.append(bool(a))
         off += inner
-    if src:
-        C().multi_copy(src, so, dst, do, rows, cols, lds, ldd, mask)
+    _multi_copy(pieces, adds)
 
 
 def split_forward(x, outs, axis):
     outer, tot = _outer_inner(x.shape, axis)
-    src, so, dst, do, rows, cols, lds, ldd = [], [], [], [], [], [], [], []
+    pieces = []
     off = 0
     for y in outs:
         _, inner = _outer_inner(y.shape, axis)
-        src.append(x); so.append(off); dst.append(y); do.append(0)
-        rows.append(outer); cols.append(inner); lds.append(tot); ldd.append(inner)
+        pieces.append((x, off, y, 0, outer, inner, tot, inner))
         off += inner
-    C().multi_copy(src, so, dst, do, rows, cols, lds, ldd, 0)
+    _multi_copy(pieces, [False] * len(pieces))
 
 
 def split_backward(out_grads, dx, acc, axis, out_shapes=None):
     """dx = concat(out_grads) along axis; a None grad (an unused split output) is a zero
     block -- the caller zeroes dx first when it does not accumulate."""
     outer, tot = _outer_inner(dx.shape, axis)
-    src, so, dst, do, rows, cols, lds, ldd = [], [], [], [], [], [], [], []
+    pieces = []
     off = 0
-    mask = 0
     for k, g in enumerate(out_grads):
         if g is None:
+            assert out_shapes is not None, "split_backward: output shapes needed to skip an unused output"
             off += _outer_inner(out_shapes[k], axis)[1]
             continue
         _, inner = _outer_inner(g.shape, axis)
-        src.append(g); so.append(0); dst.append(dx); do.append(off)
-        rows.append(outer); cols.append(inner); lds.append(inner); ldd.append(tot)
-        if acc:
-            mask |= 1 << k
+        pieces.append((g, 0, dx, off, outer, inner, inner, tot))
         off += inner
-    if src:
-        C().multi_copy(src, so, dst, do, rows, cols, lds, ldd, mask)
+    _multi_copy(pieces, [bool(acc)] * len(pieces))
 
 
 def copy_or_add(src, dst, acc):
     n = src.numel()
-    C().multi_copy([src.contiguous()], [0], [dst], [0], [1], [n], [n], [n], 1 if acc else 0)
+    _multi_copy([(src.contiguous(), 0, dst, 0, 1, n, n, n)], [bool(acc)])
 
 
 def permute(x, y, perm, acc):
@@ -1016,6 +1022,14 @@ def pool2d_backward(x, y, dy, dx, k, stride, pads, pool_type, act, acc, saved=No
     code = _pool_code(saved, y)
     C().pool_bwd(x, y, dy, dx, code, ready, k[0], k[1], stride[0], stride[1], pads[0], pads[2], int(pool_type) == 30,
                  int(act), bool(acc))
+
+
+def pool_last_form():
+    """The kernels this thread's last pool2d_forward / pool2d_backward ran (csrc/kernels/cnn.hip):
+    ``{"fwd": (form, nbands, G), "bwd": (form, nbands, G)}`` with the forward forms "planes" (several
+    whole planes per block, G > 1), "band" and "per_output", the backward forms "scatter", "band" and
+    "rows"; nbands = row bands per plane, 0 where the kernel has none."""
+    return C().pool_last_form()
 
 
 def _bn_bufs(saved, C_, device):

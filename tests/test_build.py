@@ -9,7 +9,8 @@ def test_hip_extension_loads(native):
     assert C.arch == "gfx950"
     for name in ("gemm", "embedding_fwd_multi", "embedding_bwd_multi", "dot_fwd", "dot_bwd", "sgd", "adam", "loss",
                  "im2col", "col2im", "transpose_batched", "pool_fwd", "pool_bwd", "bn_fwd", "bn_bwd", "skinny_fwd",
-                 "skinny_bwd", "multi_copy", "softmax", "dropout", "permute", "init_fill"):
+                 "skinny_bwd", "multi_copy", "softmax", "dropout", "permute", "init_fill",
+                 "pool_last_form"):
         assert hasattr(C, name), name
     out = subprocess.run(["nm", "-D", "--undefined-only", C.__file__], capture_output=True, text=True).stdout
     assert "fm_" not in out, "unresolved kernel launcher symbols:\n" + out

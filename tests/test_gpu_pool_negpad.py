@@ -1,8 +1,9 @@
-"""Pooling (row-segment backward) and convolution with NEGATIVE top/left pads against float64
-torch oracles.  A spatially split conv / pool may read its producer's buffer in place when the
-buffer box is a superset of the halo box (executor.superset_input_ok): the op then runs with
-negative pads, i.e. its first window starts inside the buffer.  Also widths that the
-backward's 8-column segments do not divide, accumulation into dx, max and avg."""
+"""Pooling and convolution with NEGATIVE top/left pads against float64 torch oracles.  A spatially
+split conv / pool may read its producer's buffer in place when the buffer box is a superset of the
+halo box (executor.superset_input_ok): the op then runs with negative pads, i.e. its first window
+starts inside the buffer.  Also odd widths, accumulation into dx, max and avg.  Every
+pooling shape here is one row band per plane and runs the band kernels (max backward: the scatter);
+the row-segment backward these shapes once reached is covered by tests/test_gpu_pool_bn_forms.py."""
 import pytest
 import torch
 import torch.nn.functional as F
