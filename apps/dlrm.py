@@ -12,8 +12,12 @@ ring, ``HDF5DLRMData``), otherwise on random data of ``--data-size`` samples (de
 GPUs, dlrm.cc:273-282); ``--loss-threshold t`` clamps predictions to [t, 1-t] in the loss.  The
 loop is the reference's (dlrm.cc:160-195): per epoch ``num_samples / batch`` iterations of
 next_batch / forward / zero_gradients / backward / update, traced with begin/end_trace(111),
-then ``ELAPSED TIME = ..., THROUGHPUT = ... samples/s``.  ``--preset`` (mlperf, mlperf_dcnv2, run_random,
-criteo_kaggle, summit, summit_large, kaggle_day1, tiny, tiny_dcn) seeds the architecture flags.
+then ``ELAPSED TIME = ..., THROUGHPUT = ... samples/s``.  ``--preset`` (mlperf, mlperf_dcnv2,
+mlperf_dcnv2_multihot, run_random, criteo_kaggle, summit, summit_large, kaggle_day1, tiny, tiny_dcn,
+tiny_dcn_multihot) seeds the architecture flags.
+``--embedding-bag-sizes 3-2-1-...`` (flexmi extension) gives every table its own bag size (the fixed
+multi-hot sizes of the MLPerf DCNv2 data set; the ``*_multihot`` presets set them); a later
+``--embedding-bag-size N`` goes back to one size for all.  X_cat of ``--dataset`` is then [N, sum of the sizes].
 ``--arch-interaction-op dcn`` (flexmi extension, with ``--arch-dcn-layers N`` and ``--arch-dcn-rank R``) puts N
 DCNv2 low-rank cross layers between the concatenation and the top MLP (MLPerf DLRM-DCNv2).
 ``--optimizer {sgd,adagrad,rowwise_adagrad}`` (flexmi extension, default sgd): Adagrad keeps one

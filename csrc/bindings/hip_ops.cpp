@@ -27,6 +27,8 @@ void fm_gemm_f32_set_split(int on);
 void fm_gemm_set_dma(int on);
 int fm_gemm_dma_enabled();
 void fm_embedding_set_bwd_mode(int count);
+void fm_embedding_set_fwd_mode(int mode);
+void fm_embedding_fwd_last_form(int* out);
 int fm_gemm_f32_get_split();
 int fm_gemm_f32_last_form();
 int fm_gemm_f32(const float* A, long lda, long sA, int a_kcontig, const float* B, long ldb, long sB, int b_kcontig,
@@ -1528,6 +1530,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_f32_get_split", []() { return fm_gemm_f32_get_split(); });
   // sparse-SGD kernels of tables with slot buffers: 1 = count / update, 0 = claim / dup / owner
   m.def("embedding_set_bwd_mode", [](bool count) { fm_embedding_set_bwd_mode(count ? 1 : 0); });
+  // forward kernel of a launch set: 0 = auto (balanced for vectorisable sets of unequal bags), 1 = never
+  // balanced, 2 = balanced for every vectorisable set
+  m.def("embedding_set_fwd_mode", [](int mode) { fm_embedding_set_fwd_mode(mode); });
+  // the kernel this thread's last forward launch set ran
+  m.def("embedding_fwd_last_form", []() {
+    int f = 0;
+    fm_embedding_fwd_last_form(&f);
+    static const char* const names[] = {"none", "multi", "multi_su", "split", "scalar", "balanced"};
+    return std::string(names[f]);
+  });
   m.def("conv_nhwc_dgrad_strided", &conv_nhwc_dgrad_strided);
   m.def("conv_nhwc_wgrad", &conv_nhwc_wgrad);
   m.def("conv_s2d", &conv_s2d);

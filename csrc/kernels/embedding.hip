@@ -11,7 +11,9 @@
 //
 // Forward: lane = 4 consecutive columns of one sample (D/4 lanes per row: a 512-B fp32 row of a
 // D=128 table is read by 32 lanes with 16-B loads), sum over the bag, bf16/fp32 output written
-// with 8/16-B stores straight into the consumer's buffer (row stride ldo).
+// with 8/16-B stores straight into the consumer's buffer (row stride ldo).  Tables of one bag size
+// get the same grid each (blockIdx.y = table); tables of unequal bag sizes (per-table multi-hot sizes)
+// share a one-dimensional grid dealt out by lookups -- "work-balanced forward" below.
 // Backward (fused sparse SGD: W[idx] -= lr*scale*dy; or dense-grad accumulate when lr == null):
 //   * regular tables: one wave-instruction = 64 consecutive fp32 atomic adds (256 contiguous bytes:
 //     the full gfx950 atomic rate, MI355X_MICROARCH "Global float atomics");
@@ -219,6 +221,106 @@ __global__ void __launch_bounds__(256) fm_emb_fwd_multi_scalar(TabSet s, long B)
     }
 }
 
+// ---- work-balanced forward for tables of UNEQUAL bag sizes (per-table multi-hot sizes) --------
+// fm_emb_fwd_multi gives every table the same grid; with the MLPerf multi-hot sizes (1..100
+// lookups per sample, 214 in all) the bag-100 table does 47 % of the row reads on 1/26 of the
+// blocks.  Here the grid is one dimension and the host deals the blocks out in proportion to each
+// table's lookups (first[i] = first block of table i); a block finds its table by a wave-uniform
+// scan of first[], then strides over that table's samples with its local id and that table's
+// block count.  lpr / rpi are per table, so tables of different D share a launch.  The sums run in
+// ascending bag order with the arithmetic and the stores of fm_emb_fwd_multi: the outputs are equal
+// bit for bit.  Every load is unconditional at a clamped address (see the header).
+struct BalSet {
+  TabDesc t[MAXT];
+  int first[MAXT + 1];
+  int n;
+};
+
+template <typename OutT>
+FM_DEVICE void emb_store4(OutT* o, const f32x4_t acc) {
+  if constexpr (sizeof(OutT) == 4) {
+    *reinterpret_cast<f32x4_t*>(o) = acc;
+  } else {
+    bf16x4_t w;
+    w[0] = (short)f2bf(acc[0]); w[1] = (short)f2bf(acc[1]); w[2] = (short)f2bf(acc[2]); w[3] = (short)f2bf(acc[3]);
+    *reinterpret_cast<bf16x4_t*>(o) = w;
+  }
+}
+
+// bags of at most U lookups: S samples' index loads, then their S * U row loads in flight per lane
+template <typename OutT, bool I64, int S, int U>
+FM_DEVICE void emb_bal_short(const TabDesc& d, long B, long b_first, long bstride, int c) {
+  for (long b0 = b_first; b0 < B; b0 += S * bstride) {
+    long r[S][U];
+    bool ok[S][U];
+#pragma unroll
+    for (int q = 0; q < S; ++q) {
+      const long e0 = min(b0 + q * bstride, B - 1) * d.bag;
+#pragma unroll
+      for (int u = 0; u < U; ++u) r[q][u] = local_row(ldi<I64>(d.idx, e0 + min(u, d.bag - 1)), d.lo, d.rows, ok[q][u]);
+    }
+    f32x4_t v[S][U];
+#pragma unroll
+    for (int q = 0; q < S; ++q)
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[q][u] = *reinterpret_cast<const f32x4_t*>(d.W + r[q][u] * d.D + c);
+#pragma unroll
+    for (int q = 0; q < S; ++q) {
+      const long b = b0 + q * bstride;
+      if (b >= B) break;
+      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (u < d.bag && ok[q][u]) acc += v[q][u];
+      acc *= d.scale;
+      emb_store4<OutT>(reinterpret_cast<OutT*>(d.act) + b * d.ld + c, acc);
+    }
+  }
+}
+
+template <typename OutT, bool I64, int U>
+__global__ void __launch_bounds__(256) fm_emb_fwd_balanced(BalSet s, long B) {
+  const int bid = blockIdx.x;
+  int ti = 0;
+  for (int i = 1; i < s.n; ++i) ti += bid >= s.first[i];      // first[] ascends: wave-uniform scan
+  const TabDesc& d = s.t[ti];
+  const int lb = bid - s.first[ti], nb = s.first[ti + 1] - s.first[ti];
+  const int lpr = d.D >> 2;                        // D <= 256: one 16-B column chunk per lane
+  const int rpi = 256 / lpr;
+  const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
+  if (sub >= rpi) return;
+  const int c = lc * 4;
+  const long bstride = (long)nb * rpi, b_first = (long)lb * rpi + sub;
+  if (d.bag == 1) return emb_bal_short<OutT, I64, 4, 1>(d, B, b_first, bstride, c);
+  if (d.bag <= 4) return emb_bal_short<OutT, I64, 2, 4>(d, B, b_first, bstride, c);
+  // longer bags in chunks of U: the chunk's U row loads and the NEXT chunk's U index loads are in
+  // flight together, so a chunk costs one round trip, not an index trip and then a row trip
+  for (long b = b_first; b < B; b += bstride) {
+    const long e0 = b * d.bag;
+    long r[U];
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) r[u] = local_row(ldi<I64>(d.idx, e0 + min(u, d.bag - 1)), d.lo, d.rows, ok[u]);
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < d.bag; j += U) {
+      f32x4_t v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(d.W + r[u] * d.D + c);
+      bool okc[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        okc[u] = ok[u];
+        r[u] = local_row(ldi<I64>(d.idx, e0 + min(j + U + u, d.bag - 1)), d.lo, d.rows, ok[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (j + u < d.bag && okc[u]) acc += v[u];
+    }
+    acc *= d.scale;
+    emb_store4<OutT>(reinterpret_cast<OutT*>(d.act) + b * d.ld + c, acc);
+  }
+}
+
 template <typename GT, bool I64>
 __global__ void __launch_bounds__(256) fm_emb_bwd_atomic_multi(TabSet s, const float* __restrict__ lr, long B) {
   const TabDesc& d = s.t[blockIdx.y];
@@ -296,9 +398,53 @@ __global__ void __launch_bounds__(256) fm_emb_bwd_tiny_multi(TabSet s, const flo
   }
 }
 
+// fm_embedding_set_fwd_mode: 0 = auto (balanced for vectorisable sets of unequal bags), 1 = never
+// balanced, 2 = balanced for every vectorisable set.  Auto takes the balanced kernel because it
+// measured 226 -> 171 us (fp32 out) and 200 -> 154 us (bf16 out) on the 26 MLPerf multi-hot tables at
+// B = 8192 (224 -> 181 and 218 -> 169 us in a second session); on tiny_dcn_multihot's four tables,
+// which are launch-bound, it is 0.2-0.5 us slower (3.5-3.8 -> 4.0 us).
+int g_emb_fwd_mode = 0;
+// the chunk of the balanced kernel's bag loop: of U = 2 / 4 / 8 at 1 / 2 / 4 x the block budget, U = 2
+// at x1 measured fastest, by 1-4 % over U = 4 (profiles/emb_fwd_multihot_ab.txt; the others are deleted)
+constexpr int BAL_U = 2;
+// which kernel this thread's last forward launch set ran (fm_embedding_fwd_last_form)
+enum FwdForm { FWD_NONE = 0, FWD_MULTI, FWD_MULTI_SU, FWD_SPLIT, FWD_SCALAR, FWD_BALANCED };
+thread_local int g_emb_fwd_form = FWD_NONE;
+
+// Block shares: the budget is the grid fm_emb_fwd_multi would launch (so the forward takes the same
+// share of the chip beside the bottom-MLP GEMMs); table i gets blocks in proportion to its lookups
+// B * bag_i, at least one and at most one per rows-per-iteration of its samples.
+template <bool I64>
+void launch_balanced(const TabSet& s, int m, bool out_bf16, long B, long budget, hipStream_t st) {
+  BalSet bs;
+  long sumbag = 0;
+  for (int i = 0; i < m; ++i) sumbag += s.t[i].bag;
+  bs.first[0] = 0;
+  for (int i = 0; i < m; ++i) {
+    bs.t[i] = s.t[i];
+    const int rpi = 256 / (s.t[i].D / 4);
+    const long cap = (B + rpi - 1) / rpi;
+    const long want = (budget * s.t[i].bag + sumbag / 2) / sumbag;
+    bs.first[i + 1] = bs.first[i] + (int)std::max<long>(1, std::min(want, cap));
+  }
+  for (int i = m + 1; i <= MAXT; ++i) bs.first[i] = bs.first[m];
+  bs.n = m;
+  const dim3 grid((unsigned)bs.first[m]);
+  if (out_bf16) hipLaunchKernelGGL((fm_emb_fwd_balanced<unsigned short, I64, BAL_U>), grid, dim3(256), 0, st, bs, B);
+  else hipLaunchKernelGGL((fm_emb_fwd_balanced<float, I64, BAL_U>), grid, dim3(256), 0, st, bs, B);
+}
+
 template <bool I64>
 void launch_fwd(const TabSet& s, int m, bool vec, bool out_bf16, long B, int D0, hipStream_t st) {
   const int rpi = std::max(1, 256 / std::min(64, std::max(1, D0 / 4)));
+  bool uniform = true;
+  for (int i = 1; i < m; ++i) uniform = uniform && s.t[i].bag == s.t[0].bag;
+  if (vec && (g_emb_fwd_mode == 2 || (g_emb_fwd_mode == 0 && !uniform))) {
+    const long budget = std::max<long>(1, std::min<long>((B + rpi - 1) / rpi, 256L)) * m;
+    launch_balanced<I64>(s, m, out_bf16, B, budget, st);
+    g_emb_fwd_form = FWD_BALANCED;
+    return;
+  }
   // long bags with too few samples to fill the chip: split every bag over SP lane groups
   // (measured on summit_large, profiles/README.md)
   int minbag = 1 << 30, maxD = 0, minD = 1 << 30;
@@ -315,6 +461,7 @@ void launch_fwd(const TabSet& s, int m, bool vec, bool out_bf16, long B, int D0,
       dim3 grid((unsigned)((B + spb - 1) / spb), m);
       if (out_bf16) hipLaunchKernelGGL((fm_emb_fwd_split<unsigned short, I64>), grid, dim3(256), 0, st, s, B, sp);
       else hipLaunchKernelGGL((fm_emb_fwd_split<float, I64>), grid, dim3(256), 0, st, s, B, sp);
+      g_emb_fwd_form = FWD_SPLIT;
       return;
     }
   }
@@ -327,7 +474,9 @@ void launch_fwd(const TabSet& s, int m, bool vec, bool out_bf16, long B, int D0,
   if (vec) {
     if (out_bf16) hipLaunchKernelGGL((fm_emb_fwd_multi<unsigned short, I64>), grid, dim3(256), 0, st, s, B, su);
     else hipLaunchKernelGGL((fm_emb_fwd_multi<float, I64>), grid, dim3(256), 0, st, s, B, su);
+    g_emb_fwd_form = uniform && s.t[0].bag == 1 ? FWD_MULTI_SU : FWD_MULTI;   // su: the single-lookup loop
   } else {
+    g_emb_fwd_form = FWD_SCALAR;
     if (out_bf16) hipLaunchKernelGGL((fm_emb_fwd_multi_scalar<unsigned short, I64>), grid, dim3(256), 0, st, s, B);
     else hipLaunchKernelGGL((fm_emb_fwd_multi_scalar<float, I64>), grid, dim3(256), 0, st, s, B);
   }
@@ -943,6 +1092,11 @@ extern "C" void fm_embedding_fwd_multi(int n, const float* const* W, const void*
     }
   }
 }
+
+extern "C" void fm_embedding_set_fwd_mode(int mode) { g_emb_fwd_mode = mode == 1 || mode == 2 ? mode : 0; }
+// out[0] = the form of this thread's last forward launch set: 0 none, 1 multi, 2 multi_su, 3 split,
+// 4 scalar, 5 balanced
+extern "C" void fm_embedding_fwd_last_form(int* out) { out[0] = g_emb_fwd_form; }
 
 static int g_emb_count = 0;    // fm_embedding_set_bwd_mode: 1 = the count / update pair
 extern "C" void fm_embedding_set_bwd_mode(int count) { g_emb_count = count ? 1 : 0; }

@@ -5,8 +5,14 @@ Graph: dense input -> bottom MLP; every sparse feature -> embedding bag; feature
 TODO, caveat C3 -- or ``dcn``: the concatenation followed by ``dcn_layers`` DCNv2 low-rank cross
 layers ``x_{l+1} = x_0 * (U_l (V_l x_l) + b_l) + x_l`` of rank ``dcn_rank``, the interaction of
 MLPerf's DLRM-DCNv2 since v3.0, ``FFModel.cross_layer``); top MLP ending in a sigmoid; MSE
-(reference) or BCE (MLPerf) loss; SGD.  The bag size is one number for every table (the MLPerf
-DCNv2 data set has per-table multi-hot sizes: not provided).
+(reference) or BCE (MLPerf) loss; SGD.  The bag size is one number for every table
+(``embedding_bag_size``) or one per table (``embedding_bag_sizes``, ``--embedding-bag-sizes 3-2-1-...``:
+the fixed per-feature multi-hot sizes of the MLPerf DCNv2 data set, presets ``mlperf_dcnv2_multihot`` and
+``tiny_dcn_multihot``): sparse input ``i`` is ``[B, bag_i]``, the tables still run as one embedding group
+and the GPU forward of such a group is the work-balanced kernel ``fm_emb_fwd_balanced``
+(``csrc/kernels/embedding.hip``).  Not provided: variable-length (jagged) bags, per-table bags in the
+native engine and the C / Keras / torch.fx / ONNX surfaces, and a hand plan (``dlrm_strategy``) that
+balances by lookups instead of bytes.
 Initialisers follow ``create_mlp``/``create_emb`` (``dlrm.cc:26-47``): MLP weights
 N(0, sqrt(2/(in+out))), biases N(0, sqrt(2/out)), tables U(±sqrt(1/rows)).
 
@@ -32,6 +38,11 @@ from flexmi.parallel.layout import ParallelConfig
 MLPERF_TABLES = [39884406, 39043, 17289, 7420, 20263, 3, 7120, 1543, 63, 38532951, 2953546, 403346, 10, 2208,
                  11938, 155, 4, 976, 14, 39979771, 25641295, 39664984, 585935, 12972, 108, 36]
 # run_criteo_kaggle.sh:8 (Kaggle cardinalities)
+# Lookups per sample of the 26 sparse features in the synthetic multi-hot Criteo set of MLPerf
+# DLRM-DCNv2 (214 in all), written down from memory: they could not be checked against the benchmark's
+# sources when this was added.  The table cardinalities of the multi-hot presets stay MLPERF_TABLES
+# (the DCNv2 benchmark's own cardinalities differ slightly).
+MLPERF_MULTIHOT_SIZES = [3, 2, 1, 2, 6, 1, 1, 1, 1, 7, 3, 8, 1, 6, 9, 5, 1, 1, 1, 12, 100, 27, 10, 3, 1, 1]
 KAGGLE_TABLES = [1396, 550, 1761917, 507795, 290, 21, 11948, 608, 3, 58176, 5237, 1497287, 3127, 26, 12153, 1068715,
                  10, 4836, 2085, 4, 1312273, 17, 15, 110946, 91, 72655]
 
@@ -54,6 +65,21 @@ class DLRMConfig:
     name: str = "custom"
     dcn_layers: int = 3          # arch_interaction_op == "dcn": cross layers ...
     dcn_rank: int = 512          # ... and their rank
+    embedding_bag_sizes: List[int] = field(default_factory=list)   # one bag size per table; empty: embedding_bag_size
+
+    def bag_sizes(self):
+        """One bag size per table: ``embedding_bag_sizes`` if set, else ``embedding_bag_size`` for all."""
+        if self.embedding_bag_sizes:
+            return list(self.embedding_bag_sizes)
+        return [self.embedding_bag_size] * len(self.embedding_size)
+
+    def checked_bag_sizes(self):
+        """``bag_sizes()``, rejecting a list that does not fit the tables."""
+        bags = self.bag_sizes()
+        if len(bags) != len(self.embedding_size) or any(b < 1 for b in bags):
+            raise ValueError(f"embedding_bag_sizes has {len(bags)} entries {bags} for {len(self.embedding_size)} "
+                             f"embedding tables: one size >= 1 per table")
+        return bags
 
     @staticmethod
     def preset(name):
@@ -66,6 +92,10 @@ class DLRMConfig:
         if name == "mlperf_dcnv2":  # MLPerf DLRM-DCNv2 (v3.0 on): 3 cross layers of rank 512 over [x] + 26 tables
             return DLRMConfig(128, list(MLPERF_TABLES), [13, 512, 256, 128], [3456, 1024, 1024, 512, 256, 1], 1, -1, -1,
                               0.0, "dcn", "", -1, "bce", "mlperf_dcnv2", 3, 512)
+        if name == "mlperf_dcnv2_multihot":  # mlperf_dcnv2 with the per-table multi-hot sizes (bags are pooled:
+            c = DLRMConfig.preset("mlperf_dcnv2")   # the top-MLP widths do not change)
+            c.name, c.embedding_bag_sizes = name, list(MLPERF_MULTIHOT_SIZES)
+            return c
         if name == "criteo_kaggle":  # run_criteo_kaggle.sh
             return DLRMConfig(16, list(KAGGLE_TABLES), [13, 512, 256, 64, 16], [224, 512, 256, 1], 1, -1, -1, 0.0,
                               "cat", "", -1, "mse", "criteo_kaggle")
@@ -84,6 +114,10 @@ class DLRMConfig:
         if name == "tiny_dcn":
             return DLRMConfig(16, [100, 50, 200, 30], [13, 32, 16], [80, 32, 1], 1, -1, -1, 0.0, "dcn", "", -1, "bce",
                               "tiny_dcn", 2, 8)
+        if name == "tiny_dcn_multihot":
+            c = DLRMConfig.preset("tiny_dcn")
+            c.name, c.embedding_bag_sizes = name, [3, 1, 8, 2]
+            return c
         raise KeyError(name)
 
     @staticmethod
@@ -100,6 +134,9 @@ class DLRMConfig:
                 c.embedding_size = [int(x) for x in nx.split("-")]; i += 1
             elif a == "--embedding-bag-size":
                 c.embedding_bag_size = int(nx); i += 1
+                c.embedding_bag_sizes = []          # one size for every table again
+            elif a == "--embedding-bag-sizes":
+                c.embedding_bag_sizes = [int(x) for x in nx.split("-")]; i += 1
             elif a == "--arch-mlp-bot":
                 c.mlp_bot = [int(x) for x in nx.split("-")]; i += 1
             elif a == "--arch-mlp-top":
@@ -156,8 +193,8 @@ def build_dlrm(model, c: DLRMConfig, pad_dense=True):
     B = model.config.batchSize
     if 0.0 < c.loss_threshold < 1.0:
         model.loss_threshold = min(c.loss_threshold, 0.5)
-    sparse = [model.create_tensor([B, c.embedding_bag_size], DataType.DT_INT64, name=f"sparse{i}")
-              for i in range(len(c.embedding_size))]
+    sparse = [model.create_tensor([B, bag], DataType.DT_INT64, name=f"sparse{i}")
+              for i, bag in enumerate(c.checked_bag_sizes())]
     bot = list(c.mlp_bot)
     if pad_dense and model.config.device == "gpu":
         bot[0] = (bot[0] + 7) // 8 * 8   # 13 -> 16: 16-B aligned rows for the first GEMM (pad columns are 0)
@@ -285,7 +322,8 @@ class SyntheticDLRMData:
 
 class HDF5DLRMData:
     """``--dataset FILE``: the Criteo HDF5 layout written by ``preprocess_hdf.py`` (X_int float32
-    [N, 13] = log(1+x), X_cat int64 [N, tables*bag], y float32 [N]) and loaded by the reference
+    [N, 13] = log(1+x), X_cat int64 [N, sum of the bag sizes] -- table i reads columns [off_i, off_i +
+    bag_i), off the running sum; tables*bag columns under one bag size --, y float32 [N]) and loaded by the reference
     (``dlrm.cc:284-330`` shapes/classes checked, ``:425-483`` whole dataset read, ``:489-589``
     next_batch = consecutive samples).  flexmi memory-maps the datasets (native HDF5 reader,
     ``flexmi.utils.hdf5``) and streams batches through the native prefetch ring: each sparse
@@ -305,9 +343,12 @@ class HDF5DLRMData:
         if X_int.ndim != 2 or X_int.dtype.kind != "f" or X_int.shape[1] != cfg.mlp_bot[0]:
             raise ValueError(f"X_int must be float [N, {cfg.mlp_bot[0]}], got {X_int.dtype} {X_int.shape}")
         N = X_int.shape[0]
-        bag = cfg.embedding_bag_size
-        if X_cat.ndim != 2 or X_cat.dtype.kind not in "iu" or X_cat.shape != (N, len(sparse) * bag):
-            raise ValueError(f"X_cat must be integer [N, {len(sparse) * bag}], got {X_cat.dtype} {X_cat.shape}")
+        bags = cfg.checked_bag_sizes()
+        off = [0]
+        for b in bags:
+            off.append(off[-1] + b)
+        if X_cat.ndim != 2 or X_cat.dtype.kind not in "iu" or X_cat.shape != (N, off[-1]):
+            raise ValueError(f"X_cat must be integer [N, {off[-1]}] (bag sizes {bags}), got {X_cat.dtype} {X_cat.shape}")
         if y.shape[0] != N:
             raise ValueError("y must have one label per sample")
         self.num_samples = N if cfg.data_size <= 0 else min(N, cfg.data_size)
@@ -316,7 +357,7 @@ class HDF5DLRMData:
             raise ValueError(f"dataset has {self.num_samples} samples < batch {B}")
         self.arrays = d
         pairs = [(dense_in, X_int, (0, X_int.shape[1]))]
-        pairs += [(t, X_cat, (i * bag, (i + 1) * bag)) for i, t in enumerate(sparse)]
+        pairs += [(t, X_cat, (off[i], off[i + 1])) for i, t in enumerate(sparse)]
         pairs.append((model.get_label_tensor(), y.reshape(N, 1), (0, 1)))
         self.loader = PrefetchLoader(model, pairs, self.num_samples, shuffle=shuffle, seed=seed, depth=depth,
                                      threads=threads)

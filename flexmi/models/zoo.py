@@ -6,7 +6,8 @@ Names: ``mlp`` / ``mnist_mlp`` (examples/python/native/mnist_mlp.py), ``mnist_cn
 ``cifar10_cnn`` (examples/python/native/{mnist,cifar10}_cnn.py), ``alexnet``, ``inception_v3``,
 ``resnet50`` (examples/cpp/*), ``resnet101`` / ``densenet121`` (the standalone simulator's
 builders, scripts/simulator.cc), ``nmt`` (nmt/), ``candle_uno`` (examples/cpp/candle_uno), ``dlrm-<preset>``
-(examples/cpp/DLRM; presets in flexmi.models.dlrm).  ``small=True`` gives a reduced-size
+(examples/cpp/DLRM; presets in flexmi.models.dlrm, the per-table multi-hot ones included:
+``dlrm-mlperf_dcnv2_multihot``, ``dlrm-tiny_dcn_multihot``).  ``small=True`` gives a reduced-size
 instance of the same architecture for tests.
 """
 from __future__ import annotations

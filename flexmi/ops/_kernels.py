@@ -1032,6 +1032,19 @@ def pool_last_form():
     return C().pool_last_form()
 
 
+def embedding_set_fwd_mode(mode):
+    """Forward kernel of an embedding launch set (csrc/kernels/embedding.hip): 0 = auto (the
+    work-balanced kernel for vectorisable sets whose tables do not all have the same bag), 1 = never
+    balanced, 2 = balanced for every vectorisable set."""
+    C().embedding_set_fwd_mode(int(mode))
+
+
+def embedding_fwd_last_form():
+    """The kernel this thread's last embedding forward launch set ran: "multi", "multi_su" (all bags
+    1), "split", "scalar" or "balanced" ("none" before the first)."""
+    return C().embedding_fwd_last_form()
+
+
 def _bn_bufs(saved, C_, device):
     if "bn_stats" not in saved:
         saved["bn_stats"] = torch.zeros(2 * C_, dtype=torch.float32, device=device)

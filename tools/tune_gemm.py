@@ -42,8 +42,8 @@ def record_specs(config, batch, dtype):
     dd = np.zeros((batch, d.dims[1]), np.float32)
     dd[:, :dcfg.mlp_bot[0]] = rng.rand(batch, dcfg.mlp_bot[0])
     ex.scatter_from_host(d, dd)
-    for t, r in zip(s, dcfg.embedding_size):
-        ex.scatter_from_host(t, rng.randint(0, r, (batch, dcfg.embedding_bag_size)).astype(np.int64))
+    for t, r, bag in zip(s, dcfg.embedding_size, dcfg.bag_sizes()):
+        ex.scatter_from_host(t, rng.randint(0, r, (batch, bag)).astype(np.int64))
     ex.scatter_from_host(m.get_label_tensor(), rng.randint(0, 2, (batch, 1)).astype(np.float32))
     T.RECORD = []
     try:
