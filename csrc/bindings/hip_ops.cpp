@@ -8,6 +8,9 @@
 #include <cstring>
 #include <vector>
 
+#include "../runtime/gemm_group_plan.h"   // GemmGroupItem (plain C++)
+using flexmi::GemmGroupItem;
+
 extern "C" {
 void fm_sgd_update_segs(float* W, float* G, float* V, unsigned short* Wc, const float* lr, const long* off,
                         const long* len, int nseg, float wd, float mom, int nesterov, int zero_g, hipStream_t s);
@@ -31,6 +34,9 @@ void fm_embedding_set_fwd_mode(int mode);
 void fm_embedding_fwd_last_form(int* out);
 int fm_gemm_f32_get_split();
 int fm_gemm_f32_last_form();
+int fm_gemm_f32_grouped(const GemmGroupItem* items, int n, int a_kcontig, int b_kcontig, float* ws, long ws_bytes,
+                        int force, int cus, int* ks_out, hipStream_t stream);
+long fm_gemm_f32_grouped_count();
 int fm_gemm_f32(const float* A, long lda, long sA, int a_kcontig, const float* B, long ldb, long sB, int b_kcontig,
                 float* C, long ldc, long sC, const float* bias, int M, int N, int K, int batch, float alpha, int beta,
                 int act, float* ws, long ws_bytes, int ksplit_req, const float* act_y, long lday, int bwd_act,
@@ -276,6 +282,48 @@ int gemm(torch::Tensor A, int64_t lda, int64_t sA, bool a_kcontig, torch::Tensor
   return ks;
 }
 
+// Several plain fp32 GEMMs C_i = (beta_i ? C_i : 0) + A_i B_i of one orientation pair as one grouped
+// split-K launch of the split kernel (gemm_f32.hip fm_gemm_f32_grouped).  Returns the split depth of
+// every member, 0 for the members it did not take (all 0: nothing was launched); the caller runs those.
+std::vector<int64_t> gemm_f32_grouped(std::vector<torch::Tensor> A, std::vector<int64_t> lda, std::vector<torch::Tensor> B,
+                                      std::vector<int64_t> ldb, std::vector<torch::Tensor> C, std::vector<int64_t> ldc,
+                                      std::vector<int64_t> M, std::vector<int64_t> N, std::vector<int64_t> K,
+                                      bool a_kcontig, bool b_kcontig, std::vector<bool> beta,
+                                      std::vector<c10::optional<torch::Tensor>> rowsum_a, torch::Tensor ws, int64_t force,
+                                      int64_t cus) {
+  const size_t n = A.size();
+  TORCH_CHECK(n >= 1 && lda.size() == n && B.size() == n && ldb.size() == n && C.size() == n && ldc.size() == n &&
+                  M.size() == n && N.size() == n && K.size() == n && beta.size() == n && rowsum_a.size() == n,
+              "gemm_f32_grouped: one entry per member in every list");
+  check_cuda(ws, "ws");
+  TORCH_CHECK(ws.scalar_type() == torch::kFloat32, "gemm_f32_grouped: fp32 workspace");
+  std::vector<GemmGroupItem> items(n);
+  for (size_t i = 0; i < n; ++i) {
+    check_cuda(A[i], "A");
+    check_cuda(B[i], "B");
+    check_cuda(C[i], "C");
+    TORCH_CHECK(A[i].scalar_type() == torch::kFloat32 && B[i].scalar_type() == torch::kFloat32 &&
+                    C[i].scalar_type() == torch::kFloat32, "gemm_f32_grouped: fp32 operands and output");
+    TORCH_CHECK(M[i] > 0 && N[i] > 0 && K[i] > 0, "gemm_f32_grouped: empty member");
+    // extent checks (the kernel trusts these): last element of each operand must be inside the storage
+    const int64_t lastA = a_kcontig ? (M[i] - 1) * lda[i] + (K[i] - 1) : (K[i] - 1) * lda[i] + (M[i] - 1);
+    const int64_t lastB = b_kcontig ? (N[i] - 1) * ldb[i] + (K[i] - 1) : (K[i] - 1) * ldb[i] + (N[i] - 1);
+    TORCH_CHECK(lastA < A[i].numel() && lastB < B[i].numel(), "gemm_f32_grouped: operand too small");
+    TORCH_CHECK((M[i] - 1) * ldc[i] + (N[i] - 1) < C[i].numel(), "gemm_f32_grouped: C too small");
+    float* rs = nullptr;
+    if (rowsum_a[i].has_value() && rowsum_a[i]->defined()) {
+      TORCH_CHECK(!a_kcontig && rowsum_a[i]->scalar_type() == torch::kFloat32 && rowsum_a[i]->numel() >= M[i] &&
+                      rowsum_a[i]->is_cuda(), "gemm_f32_grouped rowsum_a: fp32 [M], MN-contiguous A");
+      rs = rowsum_a[i]->data_ptr<float>();
+    }
+    items[i] = GemmGroupItem{A[i].data_ptr<float>(), lda[i], B[i].data_ptr<float>(), ldb[i], C[i].data_ptr<float>(), ldc[i],
+                             rs, (int)M[i], (int)N[i], (int)K[i], beta[i] ? 1 : 0};
+  }
+  std::vector<int> ks(n, 0);
+  fm_gemm_f32_grouped(items.data(), (int)n, a_kcontig, b_kcontig, ws.data_ptr<float>(), ws.numel() * 4, (int)force,
+                      (int)cus, ks.data(), cur());
+  return std::vector<int64_t>(ks.begin(), ks.end());
+}
 
 // fm_sgd over disjoint [off, off + len) ranges of one flat master / grad / state / mirror set
 void sgd_segs(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, c10::optional<torch::Tensor> Wc,
@@ -1502,6 +1550,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_dw_sgd", &gemm_dw_sgd, py::arg("dpre"), py::arg("x"), py::arg("W"), py::arg("Wc"), py::arg("V"),
         py::arg("lr"), py::arg("wd"), py::arg("mom"), py::arg("nesterov"), py::arg("db"), py::arg("ws"), py::arg("cfg") = 0);
   m.def("gemm_f32_last_form", []() { return fm_gemm_f32_last_form(); });
+  m.def("gemm_f32_grouped", &gemm_f32_grouped, py::arg("A"), py::arg("lda"), py::arg("B"), py::arg("ldb"), py::arg("C"),
+        py::arg("ldc"), py::arg("M"), py::arg("N"), py::arg("K"), py::arg("a_kcontig"), py::arg("b_kcontig"),
+        py::arg("beta"), py::arg("rowsum_a"), py::arg("ws"), py::arg("force") = 0, py::arg("cus") = 0);
+  // grouped launches issued from this thread so far (a captured step counts once, at capture)
+  m.def("gemm_f32_grouped_count", []() { return (int64_t)fm_gemm_f32_grouped_count(); });
   m.def("sgd_segs", &sgd_segs);
   m.def("init_fill", &init_fill);
   m.def("smallk_fwd", &smallk_fwd);

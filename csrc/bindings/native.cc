@@ -7,6 +7,7 @@
 #include "hdf5_lite.h"
 #include "loader.h"
 #include "native_model.h"
+#include "gemm_group_plan.h"
 #include "planner.h"
 #include "shard.h"
 #include "strategy_pb.h"
@@ -107,6 +108,24 @@ PYBIND11_MODULE(_native, m) {
     const flexmi::WeightPlan p = flexmi::plan_weights(numels, cap);
     return py::make_tuple(p.offset, p.numel, p.buckets);
   });
+  // the grouped split-K GEMM plan (gemm_group_plan.h): None when the problems are not grouped, else
+  // (depths, first block ids, slab byte offsets, workspace bytes, [(problem, tile, split) of every block])
+  m.def("gemm_group_plan", [](const std::vector<int>& M, const std::vector<int>& N, const std::vector<int>& K, int cus,
+                              int64_t ws_bytes, int force) -> py::object {
+    if (M.size() != N.size() || M.size() != K.size()) throw std::invalid_argument("gemm_group_plan: M, N, K lengths");
+    flexmi::GemmGroupPlan pl;
+    if (M.size() > (size_t)flexmi::kGemmGroupMax ||
+        !flexmi::gemm_group_plan(M.data(), N.data(), K.data(), (int)M.size(), cus, (long)ws_bytes, force, pl))
+      return py::none();
+    std::vector<std::tuple<int, int, int>> where;
+    for (int b = 0; b < pl.first[pl.n]; ++b) {
+      int g, t, s;
+      flexmi::gemm_group_locate(pl, b, g, t, s);
+      where.emplace_back(g, t, s);
+    }
+    return py::make_tuple(std::vector<int>(pl.ks, pl.ks + pl.n), std::vector<int>(pl.first, pl.first + pl.n + 1),
+                          std::vector<int64_t>(pl.ws_off, pl.ws_off + pl.n), (int64_t)pl.ws_bytes, where);
+  }, py::arg("M"), py::arg("N"), py::arg("K"), py::arg("cus"), py::arg("ws_bytes"), py::arg("force") = 0);
   m.def("plan_graph", [](const std::vector<PyOp>& ops, int world, bool input_grads) {
     std::vector<flexmi::PlanOp> v;
     v.reserve(ops.size());

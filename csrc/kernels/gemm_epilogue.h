@@ -92,6 +92,20 @@ static inline void gemm_set_update(GemmEp& p, const SgdUpd* upd) {
 // the split-bf16 kernel (gemm_x3.hip) on a parameter block prepared by gemm_f32.hip
 extern "C" int fm_gemm_x3v2_launch(const GemmF* p, int bm, int bn, int a_kcontig, int b_kcontig, int sgd, hipStream_t s);
 
+// Up to GEMM_GROUP_MAX fp32 problems run by one grid (gemm_x3.hip fm_gemm_x3v2_grouped_kernel, then
+// fm_gemm_reduce_grouped below): problem g owns the flat block ids [first[g], first[g + 1]) of the
+// launch the struct is passed to (the GEMM's blocks or the reduce's) and keeps its split-K slabs
+// [ksplit][M][N] at its own 16-B aligned p[g].ws.  vec[g]: the reduce takes problem g four outputs at
+// a time (the v4 rule of launch_splitk_reduce).
+constexpr int GEMM_GROUP_MAX = 4;
+struct GemmFGroup {
+  GemmF p[GEMM_GROUP_MAX];
+  int first[GEMM_GROUP_MAX + 1];
+  int vec[GEMM_GROUP_MAX];
+  int n;
+};
+extern "C" int fm_gemm_x3v2_launch_grouped(const GemmFGroup* g, int a_kcontig, int b_kcontig, hipStream_t s);
+
 namespace {
 
 // The SGD step on W at offset o with gradient g, by update_rule.h's rule
@@ -407,6 +421,51 @@ __global__ void __launch_bounds__(256) fm_gemm_reduce_deep(P p) {
   for (int t = 1; t < RD_G; ++t) s += part[t][o];
   float v[4] = {s[0], s[1], s[2], s[3]}, cs[4] = {0.f, 0.f, 0.f, 0.f};
   gemm_out<4, SGD, false, Q_VEC>(p, (int)zb, (int)(e / p.N), (int)(e % p.N), true, v, cs);
+}
+
+// One reduce launch for the problems of a grouped GEMM (GemmFGroup, first[] = the reduce's own block
+// ranges; an unsplit member has none: its tiles stored C themselves).  Every output goes through
+// gemm_out like the single reduces, and a problem's slabs are added in the order the single reduce
+// of its depth adds them -- slab order below 16 slabs (fm_gemm_reduce), RD_G interleaved partial
+// sums added in g order from 16 up on quads (fm_gemm_reduce_deep) -- so the result is bit-identical
+// to the ungrouped GEMM of the same form and depth.
+template <class G>   // GemmFGroup (a template so that only the file that launches it compiles it)
+__global__ void __launch_bounds__(256) fm_gemm_reduce_grouped(G s) {
+  const int bid = blockIdx.x;
+  int g = 0;
+  for (int i = 1; i < s.n; ++i) g += bid >= s.first[i];      // first[] ascends: wave-uniform scan
+  const auto& p = s.p[g];
+  const int lb = bid - s.first[g], nb = s.first[g + 1] - s.first[g];
+  const long MN = (long)p.M * p.N;
+  float cs[4] = {0.f, 0.f, 0.f, 0.f};
+  if (s.vec[g]) {
+    const bool deep = p.ksplit >= 16;
+    for (long i = lb * 256L + threadIdx.x; i < MN / 4; i += nb * 256L) {
+      const long e = i * 4;
+      const float* src = p.ws + e;
+      f32x4_t t;
+      if (deep) {
+        f32x4_t part[RD_G];
+#pragma unroll
+        for (int u = 0; u < RD_G; ++u) {
+          part[u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+          for (int k = u; k < p.ksplit; k += RD_G) part[u] += *reinterpret_cast<const f32x4_t*>(src + (long)k * MN);
+        }
+        t = part[0];
+#pragma unroll
+        for (int u = 1; u < RD_G; ++u) t += part[u];
+      } else {
+        t = slab_sum4(src, MN, p.ksplit);
+      }
+      float v[4] = {t[0], t[1], t[2], t[3]};
+      gemm_out<4, false, false, Q_VEC>(p, 0, (int)(e / p.N), (int)(e % p.N), true, v, cs);
+    }
+  } else {
+    for (long e = lb * 256L + threadIdx.x; e < MN; e += nb * 256L) {
+      float v[1] = {slab_sum1(p.ws + e, MN, p.ksplit)}, c1[1] = {0.f};
+      gemm_out<1, false, false, Q_SCALAR>(p, 0, (int)(e / p.N), (int)(e % p.N), true, v, c1);
+    }
+  }
 }
 
 // The slab sums of the first nv of four adjacent columns, each column added in slab order as slab_sum1

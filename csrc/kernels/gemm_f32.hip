@@ -23,6 +23,7 @@
 // beta accumulate; dW GEMMs fold the bias gradient in as row sums of the staged A tiles.
 // Split-K writes fp32 slabs reduced by one reduce launch (gemm_epilogue.h).  XCD-aware tile order.
 #include "gemm_f32_common.h"
+#include "../runtime/gemm_group_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -536,6 +537,111 @@ static int gemm_f32_run(const float* A, long lda, long sA, int a_kcontig, const 
   else launch_fbm<64, 64>(p, a_kcontig, b_kcontig, vec, stream);
   if (ks > 1) launch_splitk_reduce(p, fused_ep, stream);
   return ks;
+}
+
+// ------------------------------------------------------------------------------------------
+// Grouped split-K launch: several plain fp32 GEMMs (batch 1, one orientation pair) that gemm_f32_run
+// would each send to the split kernel's 256x128 tile with a split depth above 1 -- the weight
+// gradients of an MLP at a big batch, 16-32 tiles each -- run as ONE grid of that kernel and one
+// reduce, at the depths of flexmi::gemm_group_plan (the three top-MLP dW GEMMs of the MLPerf DLRM
+// step: 4 / 4 / 4, 256 blocks, instead of three launches 16 / 8 / 16 deep with a reduce each).
+// Every member computes C = (beta ? C : 0) + A B and, with rowsum_a and an MN-contiguous A,
+// rowsum_a[m] += sum_k A(m, k), bit-identical to fm_gemm_f32 with ksplit = depth | 4 << 8.
+// The tuned table is not consulted: it is keyed by single GEMMs.
+using flexmi::GemmGroupItem;
+static_assert(flexmi::kGemmGroupMax == GEMM_GROUP_MAX, "the planner's member limit is the kernels' parameter-block count");
+
+static thread_local long g_grouped_launches = 0;
+extern "C" long fm_gemm_f32_grouped_count() { return g_grouped_launches; }
+
+// force = 0: the planner's depths for the eligible members; > 0: that depth for every member the
+// forced form 4 applies to (tests, tools/bench_dw_grouped.py).  cus <= 0: the device's CU count.
+// ks_out[i] = the depth member i ran at, 0 for a member left to the caller.  Returns the number of
+// members launched: 0 = not grouped, nothing was launched and the caller runs every member itself.
+extern "C" int fm_gemm_f32_grouped(const GemmGroupItem* items, int n, int a_kcontig, int b_kcontig, float* ws,
+                                   long ws_bytes, int force, int cus, int* ks_out, hipStream_t stream) {
+  for (int i = 0; i < n; ++i) ks_out[i] = 0;
+  if (ws == nullptr || (((uintptr_t)ws) & 15) != 0) return 0;
+  if (cus <= 0) {   // the current device's (the stream's): asked every call, no per-process cache
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 0;
+  }
+  const int split_mode = f32_split_mode();
+  auto al = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
+  int idx[flexmi::kGemmGroupMax], Ms[flexmi::kGemmGroupMax], Ns[flexmi::kGemmGroupMax], Ks[flexmi::kGemmGroupMax];
+  int m = 0;
+  for (int i = 0; i < n && m < flexmi::kGemmGroupMax; ++i) {
+    const GemmGroupItem& it = items[i];
+    // the rules by which gemm_f32_run takes the split kernel's 256x128 tile (heuristic, or forced form 4)
+    const bool big = std::min(it.M, it.N) >= 480 && it.K >= 480;
+    const bool x3_pick = force > 0 ? split_mode != 0
+                                   : split_mode == 2 || split_mode == 5 || ((split_mode == 3 || split_mode == 4) && big);
+    const bool f16_pick = split_mode >= 4 && (a_kcontig || split_mode == 5);   // runs on 128-row tiles
+    if (!x3_pick || f16_pick || it.K <= 0 || it.K % 32 != 0 || it.M < 64 || it.N < 64) continue;
+    if (force <= 0 && it.M < 256) continue;
+    if ((a_kcontig && !(al(it.A) && it.lda % 4 == 0)) || (b_kcontig && !(al(it.B) && it.ldb % 4 == 0))) continue;
+    if (it.rowsum_a != nullptr && a_kcontig) continue;
+    const long tiles = (long)((it.M + 255) / 256) * ((it.N + 127) / 128);
+    if (force <= 0 && !(tiles < 256 && 2 <= it.K / 32 / 4)) continue;   // its own depth would be 1
+    // members of one launch are reduced concurrently: an output (or row-sum vector) that overlaps an
+    // earlier member's -- the gradient buffer of a weight shared by two layers -- stays with the caller,
+    // who runs it after this launch (C = C + A B accumulates in launch order, as the per-layer path does)
+    auto overlaps = [](const float* a, long na, const float* b, long nb) { return a < b + nb && b < a + na; };
+    bool shared = false;
+    for (int j = 0; j < m && !shared; ++j) {
+      const GemmGroupItem& o = items[idx[j]];
+      shared = overlaps(it.C, (long)(it.M - 1) * it.ldc + it.N, o.C, (long)(o.M - 1) * o.ldc + o.N);
+    }
+    if (shared) continue;
+    idx[m] = i; Ms[m] = it.M; Ns[m] = it.N; Ks[m] = it.K;
+    ++m;
+  }
+  flexmi::GemmGroupPlan pl;
+  if (!flexmi::gemm_group_plan(Ms, Ns, Ks, m, cus, ws_bytes, force, pl)) return 0;
+  GemmFGroup grp;
+  grp.n = m;
+  for (int g = 0; g < m; ++g) {
+    const GemmGroupItem& it = items[idx[g]];
+    GemmF& p = grp.p[g];
+    p.A = it.A; p.lda = it.lda; p.sA = 0;
+    p.B = it.B; p.ldb = it.ldb; p.sB = 0;
+    p.C = it.C; p.ldc = it.ldc; p.sC = 0;
+    p.bias = nullptr; p.ay = nullptr; p.lday = 0; p.colsum = nullptr; p.rowsum_a = it.rowsum_a;
+    p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + pl.ws_off[g]);
+    p.bact = ACT_NONE; p.act = ACT_NONE; p.M = it.M; p.N = it.N; p.K = it.K; p.beta = it.beta; p.batch = 1;
+    p.alpha = 1.f;
+    p.n_fast = it.M >= it.N;
+    gemm_set_update(p, nullptr);
+    p.dma = 0;
+    p.amax_a = p.amax_b = nullptr;
+    p.amax_na = p.amax_nb = 1;
+    p.tiles_m = (it.M + 255) / 256;
+    p.tiles_n = (it.N + 127) / 128;
+    p.ksplit = pl.ks[g];
+    grp.first[g] = pl.first[g];
+    grp.vec[g] = 0;
+    ks_out[idx[g]] = pl.ks[g];
+  }
+  grp.first[m] = pl.first[m];
+  if (fm_gemm_x3v2_launch_grouped(&grp, a_kcontig, b_kcontig, stream) != 0) {
+    for (int i = 0; i < n; ++i) ks_out[i] = 0;
+    return 0;
+  }
+  // one reduce over every split member: blocks of 256 threads, a quad (or one output) per thread
+  int nb = 0;
+  for (int g = 0; g < m; ++g) {
+    const GemmF& p = grp.p[g];
+    grp.first[g] = nb;
+    grp.vec[g] = (p.N % 4 == 0) && (p.ldc % 4 == 0) && al(p.C);
+    if (p.ksplit > 1) nb += fm_grid((long)p.M * p.N / (grp.vec[g] ? 4 : 1), 256, 1024);
+  }
+  grp.first[m] = nb;
+  if (nb > 0) hipLaunchKernelGGL((fm_gemm_reduce_grouped<GemmFGroup>), dim3(nb), dim3(256), 0, stream, grp);
+  g_last_form = 4;
+  ++g_grouped_launches;
+  return m;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -186,8 +186,11 @@ struct X3Stage {
   }
 };
 
-template <int BM, int BN, bool AK, bool BKC, bool SGD, int SCHED, bool F16 = false>
-__global__ void __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) fm_gemm_x3v2_kernel(GemmF p) {
+// One block's work: output tile `tile_id` (in launch order: remapped over the problem's own tile
+// count) of batch zb, k range `split` of p.ksplit.  The single-problem kernel and the grouped one
+// (several problems' tiles in one grid) below both run it.
+template <int BM, int BN, bool AK, bool BKC, bool SGD, int SCHED, bool F16>
+FM_DEVICE void x3v2_tile(const GemmF& p, int tile_id, int zb, int split) {
   constexpr int WM = BM / 64, WN = BN / 64, NTH = WM * WN * 64;
   constexpr int MR = 4, NR = 4;
   constexpr int NPL = F16 ? 2 : 3;                     // planes per operand
@@ -196,10 +199,9 @@ __global__ void __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) fm_gemm_x3v2_ke
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+  const int bid = xcd_remap(tile_id, p.tiles_m * p.tiles_n);
   const TileMN tile = tile_coords(p, bid);
   const int tm = tile.m, tn = tile.n;
-  const int zb = blockIdx.y, split = blockIdx.z;
   const int m0 = tm * BM, n0 = tn * BN;
   const float* A = p.A + (long)zb * p.sA;
   const float* B = p.B + (long)zb * p.sB;
@@ -375,6 +377,26 @@ __global__ void __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) fm_gemm_x3v2_ke
   gemm_epilogue<MR, NR, false, false, SGD>(p, acc, zb, split, m0 + wm * 64, n0 + wn * 64, lane);
 }
 
+template <int BM, int BN, bool AK, bool BKC, bool SGD, int SCHED, bool F16 = false>
+__global__ void __launch_bounds__((BM / 64) * (BN / 64) * 64, 1) fm_gemm_x3v2_kernel(GemmF p) {
+  x3v2_tile<BM, BN, AK, BKC, SGD, SCHED, F16>(p, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+// Several split-K problems (batch 1, one orientation pair) in one grid of 256x128 schedule-3 tiles:
+// problem g owns the flat block ids [first[g], first[g + 1]), local id -> (split, tile) with the tile
+// fastest, each problem in its own tile order and with its own slabs (p.ws).  The top-MLP weight
+// gradients of a DLRM step are 16 + 32 + 16 tiles: alone each splits K 8- or 16-fold to fill the
+// chip, together they fill it at 4-fold with a quarter of the fixed per-block cost and slab traffic.
+template <bool AK, bool BKC>
+__global__ void __launch_bounds__(512, 1) fm_gemm_x3v2_grouped_kernel(GemmFGroup s) {
+  const int bid = blockIdx.x;
+  int g = 0;
+  for (int i = 1; i < s.n; ++i) g += bid >= s.first[i];      // first[] ascends: wave-uniform scan
+  const GemmF& p = s.p[g];
+  const int lb = bid - s.first[g], tiles = p.tiles_m * p.tiles_n;
+  x3v2_tile<256, 128, AK, BKC, false, 3, false>(p, lb % tiles, 0, lb / tiles);
+}
+
 template <int BM, int BN, bool SGD, int SCHED, bool F16 = false>
 void launch_x3v2_s(const GemmF& p, bool ak, bool bk, hipStream_t s) {
   constexpr int NTH = (BM / 64) * (BN / 64) * 64;
@@ -443,5 +465,35 @@ extern "C" int fm_gemm_x3v2_launch(const GemmF* params, int bm, int bn, int a_kc
   } else {
     return -1;
   }
+  return 0;
+}
+
+// The grouped launch on prepared parameter blocks (gemm_f32.hip fm_gemm_f32_grouped): every block
+// filled for the 256x128 tile with its own ksplit and slab base, first[] = prefix sums of
+// tiles * ksplit, no fused SGD, batch 1.
+extern "C" int fm_gemm_x3v2_launch_grouped(const GemmFGroup* group, int a_kcontig, int b_kcontig, hipStream_t s) {
+  const GemmFGroup& g = *group;
+  if (g.n < 1 || g.n > GEMM_GROUP_MAX) return -1;
+  for (int i = 0; i < g.n; ++i)
+    if (g.p[i].uw != nullptr || g.p[i].batch != 1 || g.p[i].amax_a != nullptr ||
+        g.first[i + 1] - g.first[i] != g.p[i].tiles_m * g.p[i].tiles_n * g.p[i].ksplit)
+      return -1;
+  constexpr int LDS = 2 * 3 * (256 + 128) * 64;
+  const dim3 grid(g.first[g.n]);
+#define FM_X3G(AKv, BKv)                                                                                          \
+  do {                                                                                                            \
+    static bool attr = false;                                                                                     \
+    if (!attr) {                                                                                                  \
+      (void)hipFuncSetAttribute((const void*)fm_gemm_x3v2_grouped_kernel<AKv, BKv>,                               \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS);                                 \
+      attr = true;                                                                                                \
+    }                                                                                                             \
+    hipLaunchKernelGGL((fm_gemm_x3v2_grouped_kernel<AKv, BKv>), grid, dim3(512), LDS, s, g);                      \
+  } while (0)
+  if (a_kcontig && b_kcontig) FM_X3G(true, true);
+  else if (a_kcontig) FM_X3G(true, false);
+  else if (b_kcontig) FM_X3G(false, true);
+  else FM_X3G(false, false);
+#undef FM_X3G
   return 0;
 }

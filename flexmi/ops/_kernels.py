@@ -255,6 +255,66 @@ def linear_backward(x2, w, y2, dy2, act, dx2, dx_acc, dw, db, ws, grad_is_dpre=F
         _linear_dx(dpre, w, dx2, dx_acc, fuse_below, M, N, K)
 
 
+def gemm_grouped(members, a_kcontig, b_kcontig, force=0, cus=0):
+    """Several plain fp32 GEMMs ``C = (beta ? C : 0) + A B`` of one orientation pair as ONE grouped
+    split-K launch of the split kernel and one reduce (csrc/kernels/gemm_f32.hip fm_gemm_f32_grouped).
+    members = [(A, lda, B, ldb, C, ldc, M, N, K, beta, rowsum_a)].  Returns every member's split depth,
+    0 for the members the kernel did not take -- the caller runs those; all 0: nothing was launched.
+    force > 0: that depth for every member the 256x128 tile applies to (tests, tools/bench_dw_grouped.py)."""
+    f = list(zip(*members))
+    return C().gemm_f32_grouped(list(f[0]), list(f[1]), list(f[2]), list(f[3]), list(f[4]), list(f[5]), list(f[6]),
+                                list(f[7]), list(f[8]), bool(a_kcontig), bool(b_kcontig), [bool(x) for x in f[9]],
+                                list(f[10]), workspace(members[0][4].device, GEMM_WS_BYTES), int(force), int(cus))
+
+
+def dw_group_candidate(x2, out_dim):
+    """Whether the dW GEMM of a Linear layer with input ``x2`` [batch, in] could join a grouped launch
+    (the executor's compile-time filter: a superset of what fm_gemm_f32_grouped accepts -- fp32, not a
+    skinny / thin-input / library layer, inside the split kernel's policy, whole 32-deep k steps)."""
+    M, K = x2.shape
+    if x2.dtype != torch.float32 or out_dim < 256 or K < 64 or M % 32 != 0 or _smallk(x2, K) or _dw_lib(M, out_dim, K, x2.dtype):
+        return False
+    # alone it would split K on the 256x128 tile (gemm_f32_run: fewer than 256 tiles, at least 8 k steps):
+    # a layer that fills the device by itself keeps its place in the backward
+    if M < 256 or ((out_dim + 255) // 256) * ((K + 127) // 128) >= 256:
+        return False
+    mode = C().gemm_f32_get_split()
+    return mode in (2, 5) or (mode in (3, 4) and min(out_dim, K) >= 480 and M >= 480)
+
+
+def linear_dw_group(calls):
+    """The "dw" phases of several Linear layers, ``calls`` = one linear_backward argument tuple each
+    (the executor's FM_DW_GROUP flush).  The fp32 members whose dW GEMM would go to the split kernel's
+    256x128 tile with a split depth above 1 run as one grouped launch (gemm_grouped decides: two members
+    at least, at most four a launch); bf16 layers, the skinny and thin-input layers, the library path,
+    fused SGD and whatever the kernel declines run as their own "dw" phase, in order.  The kernel never
+    takes two members whose dW buffers overlap (layers sharing a weight accumulate into one gradient):
+    the later one waits for the next launch or runs alone.  Any number of layers: the kernel takes up
+    to four of the list per call.  Returns the number of members that ran grouped."""
+    cand = []
+    for i, a in enumerate(calls):
+        x2, w, dy2, act, dw, db, ws, grad_is_dpre, upd = a[0], a[1], a[3], a[4], a[7], a[8], a[9], a[10], a[13]
+        M, K = x2.shape
+        N = w.shape[0]
+        if (upd is None and x2.dtype == torch.float32 and M > 0 and N > 1 and not _smallk(x2, K)
+                and not _dw_lib(M, N, K, x2.dtype) and x2.stride(1) == 1):
+            dpre = dy2 if (grad_is_dpre or act == 10) else ws["dpre"]
+            # dW[N,K] += dpre^T x, db += column sums of dpre: as linear_backward's own GEMM
+            cand.append((i, (dpre, dpre.stride(0), x2, x2.stride(0), dw, K, N, K, M, True, db)))
+    grouped = set()
+    while len(cand) >= 2:
+        ks = gemm_grouped([c[1] for c in cand], False, False)
+        took = {c[0] for c, k in zip(cand, ks) if k > 0}
+        if not took:
+            break
+        grouped |= took
+        cand = [c for c in cand if c[0] not in took]
+    for i, a in enumerate(calls):
+        if i not in grouped:
+            linear_backward(*a)
+    return len(grouped)
+
+
 def _linear_dx(dpre, w, dx2, dx_acc, fuse_below, M, N, K):
     # dX[M,K] = dpre W   (+ fused activation backward of the layer below)
     if dx2 is not None:

@@ -111,9 +111,10 @@ class Linear(Op):
             out = torch.nn.functional.linear(x2.float(), ctx.wcompute[0].float(), None if b is None else b.float())
             y2.copy_(act_forward_torch(out, self.activation))
 
-    def backward(self, ctx: OpCtx, phase="all"):
+    def backward(self, ctx: OpCtx, phase="all", collect=None):
         """phase "dx": input gradient (and the shared act-bwd); "dw": weight / bias gradients --
-        the executor runs dW later to overlap a pending gradient exchange; "all": both."""
+        the executor runs dW later to overlap a pending gradient exchange; "all": both.
+        collect (HIP): a list that takes this call's kernel arguments instead of running them."""
         x = ctx.inputs[0]
         x2 = x.reshape(-1, x.shape[-1])
         y2 = ctx.outputs[0].view(-1, ctx.outputs[0].shape[-1])
@@ -124,10 +125,14 @@ class Linear(Op):
         db = ctx.weight_grads[1] if self.use_bias else None
         act = ActiMode.AC_MODE_NONE if getattr(self, "skip_act_grad", False) else self.activation
         if ctx.hip:
-            K.linear_backward(x2, ctx.wcompute[0], y2, dy2, int(act), dx2,
-                              bool(ctx.in_grad_accumulate[0]) if dx2 is not None else False, dw, db,
-                              ctx.workspace, ctx.saved.get("grad_is_dpre", False), ctx.saved.get("fuse_below"), phase,
-                              upd=_armed_sgd(ctx))
+            args = (x2, ctx.wcompute[0], y2, dy2, int(act), dx2,
+                    bool(ctx.in_grad_accumulate[0]) if dx2 is not None else False, dw, db,
+                    ctx.workspace, ctx.saved.get("grad_is_dpre", False), ctx.saved.get("fuse_below"), phase,
+                    _armed_sgd(ctx))
+            if collect is not None:
+                collect.append(args)
+                return
+            K.linear_backward(*args)
         else:
             dpre = act_backward_torch(dy2.float(), y2.float(), act)
             if phase != "dx":
@@ -136,6 +141,20 @@ class Linear(Op):
                     db.add_(dpre.sum(0))
             if dx2 is not None and phase != "dw":
                 store(dx2, dpre @ ctx.wcompute[0].float(), ctx.in_grad_accumulate[0])
+
+    @staticmethod
+    def backward_dw_group(pairs):
+        """The "dw" phases of the Linear ops ``pairs`` = [(op, ctx)] (an MLP in backward order) at once:
+        on the HIP backend the weight-gradient GEMMs that qualify run as one grouped launch
+        (K.linear_dw_group), every other member as its own "dw" phase."""
+        calls = []
+        for op, c in pairs:
+            if c.hip:
+                op.backward(c, "dw", collect=calls)
+            else:
+                op.backward(c, "dw")
+        if calls:
+            K.linear_dw_group(calls)
 
     def flops(self, in_shapes, out_shapes):
         b = 1

@@ -1762,6 +1762,30 @@ class Executor:
         mode = os.environ.get("FLEXMI_DEFER_DW", "1")     # 0: off, force: also without an exchange (tests)
         defer_ok = (has_xchg or mode == "force") and mode != "0"
         deferred = []          # [(op, ctx)] whose dW items wait for the first exchange start
+        # FM_DW_GROUP (default on; HIP backend, fp32 compute): the Linear ops of a run of consecutive
+        # Linear ops in backward order (an MLP) whose dW GEMM could join a grouped launch emit their
+        # dX phases at once and their dW phases together where the run ends, or where the deferred
+        # dW items above are flushed -- there the weight-gradient GEMMs the kernel accepts go out
+        # as ONE grouped split-K launch (ops/_kernels.py linear_dw_group), the rest as they always
+        # did.  Layers outside the filter (the DLRM bottom MLP beside the table backward, the
+        # narrow end of the top MLP) keep their place and order.
+        group_on = (self.backend == "hip" and self.cdtype == torch.float32 and mode != "0"
+                    and os.environ.get("FM_DW_GROUP", "1") != "0")
+
+        def plain_linear(st):
+            if st[0] != "op" or st[1].op_type != OperatorType.OP_LINEAR or not st[1].weights:
+                return False
+            o, c = st[1], self.ctx.get(st[1].guid)
+            if (c is None or self.group_of.get(o.guid) is not None or (getattr(o, "rule", None) and o.rule.replicas)
+                    or getattr(c, "empty", False) or not c.inputs or c.inputs[0] is None):
+                return False
+            from flexmi.ops import _kernels as K
+            x = c.inputs[0]
+            return K.dw_group_candidate(x.reshape(-1, x.shape[-1]), o.out_dim)
+
+        in_run = [group_on and plain_linear(st) for st in steps]
+        in_run = [r and ((k > 0 and in_run[k - 1]) or (k + 1 < len(steps) and in_run[k + 1]))
+                  for k, r in enumerate(in_run)]
 
         def bucket_done(done_ops):
             for w in [w for o in done_ops for w in o.weights]:
@@ -1782,6 +1806,13 @@ class Executor:
                                                 f"allreduce.bucket{bi}", native=("ar", g, bi)))
 
         def flush_deferred():
+            if group_on and len(deferred) > 1:
+                pairs = list(deferred)
+                C(bwd, pairs[0][0].name + ".grouped.bwd_dw", (lambda pairs=pairs: type(pairs[0][0]).backward_dw_group(pairs)))
+                for dop, _ in pairs:
+                    bucket_done([dop])
+                deferred.clear()
+                return
             for dop, dc in deferred:
                 C(bwd, dop.name + ".bwd_dw", (lambda op=dop, c=dc: op.backward(c, "dw")))
                 bucket_done([dop])
@@ -1795,6 +1826,8 @@ class Executor:
                 self._emit_exchange_finish(bwd, ex, "reshard.bwd")
             if k < skip_to:
                 continue
+            if deferred and not defer_ok and not (group_on and in_run[k] and k != kb):
+                flush_deferred()          # the run of Linear ops ended
             if k == kb:
                 skip_to = self._emit_pipelined_bwd(bwd, C, pipe, k, written, bucket_done, finish_before, touches)
                 if defer_ok:
@@ -1820,7 +1853,7 @@ class Executor:
                         if grp[0] is op:
                             C(bwd, op.name + ".group_bwd",
                               (lambda grp=grp: type(grp[0]).backward_group(grp, [self.ctx[o.guid] for o in grp])))
-                    elif defer_ok and op.op_type == OperatorType.OP_LINEAR and op.weights:
+                    elif (defer_ok or (group_on and in_run[k])) and op.op_type == OperatorType.OP_LINEAR and op.weights:
                         C(bwd, op.name + ".bwd_dx", (lambda op=op, c=c, flags=flags: self._bwd_op(op, c, flags, "dx")))
                         bwd[-1].check = (lambda op=op, c=c: self._check_op(op.name + ".bwd", c.in_grads, "input grad"))
                         deferred.append((op, c))
