@@ -1,203 +1,27 @@
 // pybind11 bindings of the flexmi HIP kernels (module flexmi._C).
 // Kernels live in csrc/kernels/*.hip behind extern "C" launchers (compiled with hipcc for gfx950
-// only, no torch headers); this file only unpacks torch tensors into raw pointers and launches on
-// PyTorch's current HIP stream, so kernels compose with torch's caching allocator, RCCL streams
-// and hipGraph capture.
+// only, no torch headers), all declared in csrc/kernels/launchers.h, which the definitions are
+// compiled against too; this file declares none itself.  It only unpacks torch tensors into raw
+// pointers and launches on PyTorch's current HIP stream, so kernels compose with torch's caching
+// allocator, RCCL streams and hipGraph capture.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <cstring>
 #include <vector>
 
-#include "../runtime/gemm_group_plan.h"   // GemmGroupItem (plain C++)
+#include "../kernels/launchers.h"
 using flexmi::GemmGroupItem;
-
-extern "C" {
-void fm_sgd_update_segs(float* W, float* G, float* V, unsigned short* Wc, const float* lr, const long* off,
-                        const long* len, int nseg, float wd, float mom, int nesterov, int zero_g, hipStream_t s);
-void fm_image_normalize(const unsigned char* src, void* dst, long N, int H, int W, const float* mean, const float* stdv,
-                        int bf16, hipStream_t s);
-int fm_gemm_dw_sgd(const void* A, long lda, const void* B, long ldb, float* W, long ldw, unsigned short* Wc, float* V,
-                   const float* lr, float wd, float mom, int nesterov, int M, int N, int K, float* ws, long ws_bytes,
-                   float* rowsum_a, int cfg, hipStream_t stream);
-int fm_gemm_f32_dw_sgd(const float* A, long lda, const float* B, long ldb, float* W, long ldw, unsigned short* Wc,
-                       float* V, const float* lr, float wd, float mom, int nesterov, int M, int N, int K, float* ws,
-                       long ws_bytes, float* rowsum_a, int cfg, hipStream_t stream);
-int fm_gemm(const void* A, long lda, long sA, int a_kcontig, const void* B, long ldb, long sB, int b_kcontig, void* C,
-            long ldc, long sC, int c_fp32, const float* bias, int M, int N, int K, int batch, float alpha, int beta,
-            int act, float* ws, long ws_bytes, int ksplit_req, const void* act_y, long lday, int bwd_act,
-            float* colsum, float* rowsum_a, hipStream_t stream);
-void fm_gemm_f32_set_split(int on);
-void fm_gemm_set_dma(int on);
-int fm_gemm_dma_enabled();
-void fm_embedding_set_bwd_mode(int count);
-void fm_embedding_set_fwd_mode(int mode);
-void fm_embedding_fwd_last_form(int* out);
-int fm_gemm_f32_get_split();
-int fm_gemm_f32_last_form();
-int fm_gemm_f32_grouped(const GemmGroupItem* items, int n, int a_kcontig, int b_kcontig, float* ws, long ws_bytes,
-                        int force, int cus, int* ks_out, hipStream_t stream);
-long fm_gemm_f32_grouped_count();
-int fm_gemm_f32(const float* A, long lda, long sA, int a_kcontig, const float* B, long ldb, long sB, int b_kcontig,
-                float* C, long ldc, long sC, const float* bias, int M, int N, int K, int batch, float alpha, int beta,
-                int act, float* ws, long ws_bytes, int ksplit_req, const float* act_y, long lday, int bwd_act,
-                float* colsum, float* rowsum_a, hipStream_t stream);
-int fm_smallk_fwd_launch(const void* x, long ldx, const void* w, const float* bias, void* y, long ldy, long M, int K, int N,
-                         int act, int bf16, hipStream_t s);
-int fm_smallk_dw_launch(const void* dpre, long ldd, const void* x, long ldx, float* dw, float* db, long M, int K, int N,
-                        float* ws, long ws_bytes, float* V, unsigned short* Wc, const float* lr, float wd, float mom,
-                        int nesterov, int bf16, hipStream_t s);
-void fm_skinny_fwd_f32_launch(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, long B, int K,
-                              int act, hipStream_t s);
-void fm_skinny_bwd_f32_launch(const float* x, long ldx, const float* w, const float* y, long ldy, const float* dy, long lddy,
-                              float* dx, long lddx, int dx_acc, float* dw, float* db, long B, int K, int act, int bact,
-                              hipStream_t s);
-void fm_skinny_fwd(const void* x, long ldx, const void* w, const float* bias, void* y, long ldy, long B, int K, int act,
-                   hipStream_t s);
-void fm_skinny_bwd(const void* x, long ldx, const void* w, const void* y, long ldy, const void* dy, long lddy, void* dx,
-                   long lddx, int dx_acc, float* dw, float* db, long B, int K, int act, int bact, hipStream_t s);
-void fm_init_fill(float* out, long rows, long cols, long r0, long c0, long ldg, int kind, unsigned seed, float a, float b,
-                  hipStream_t s);
-void fm_embedding_fwd(const void* idx, int idx64, const float* W, void* out, int out_bf16, long B, int bag, int rows, int D,
-                      long ldo, float scale, hipStream_t s);
-void fm_embedding_bwd(const void* idx, int idx64, const void* dy, int dy_bf16, float* W, const float* lr, long B, int bag,
-                      int rows, int D, long ldg, float scale, hipStream_t s);
-void fm_embedding_fwd_multi(int n, const float* const* W, const void* const* idx, const int* idx64, void* const* out,
-                            const long* ldo, const long* lo, const int* rows, const int* D, const int* bag,
-                            const float* scale, int out_bf16, long B, hipStream_t st);
-void fm_embedding_bwd_multi(int n, float* const* W, const void* const* idx, const int* idx64, const void* const* dy,
-                            const long* ldg, const long* lo, const int* rows, const int* D, const int* bag,
-                            const float* scale, int dy_bf16, const float* lr, long B, int* const* owner,
-                            int* const* dups, int* const* ndup, hipStream_t st);
-void fm_sdp_coalesce(int n, const void* const* idx, const int* idx64, const void* const* dy, const long* ldg,
-                     const long* lo, const int* rows, const int* D, const int* bag, const float* scale, int dy_bf16, long B,
-                     int* const* slot, int* const* cid, int* const* ids, float* const* g, int* const* count, hipStream_t st);
-void fm_sdp_apply_segments(int n, int segs, int own_seg, float* const* W, const int* D, const int* const* seg_ids,
-                           const float* const* seg_g, const int* const* seg_count, int* const* slot, int* const* own_count,
-                           const int* nmax, const float* lr, hipStream_t st);
-void fm_emb_adagrad_apply(int n, float* const* W, float* const* H, const int* D, const int* const* ids,
-                          const float* const* g, int* const* count, int* const* slot, const int* nmax, const float* lr,
-                          float eps, hipStream_t st);
-void fm_emb_rowwise_adagrad_apply(int n, float* const* W, float* const* h, const int* D, const int* const* ids,
-                                  const float* const* g, int* const* count, int* const* slot, const int* nmax,
-                                  const float* lr, float eps, hipStream_t st);
-void fm_sdp_rowwise_merge_segments(int n, int segs, const int* rows, const int* D, const int* const* seg_ids,
-                                   const float* const* seg_g, const int* const* seg_count, const int* const* own_ids,
-                                   int* const* own_count, int* const* slot, int* const* mids, float* const* mg,
-                                   int* const* mcount, const int* nmax, const int* mcap, hipStream_t st);
-void fm_strided_copy4_run(const void* src, void* dst, int bf16, const int* d, const long* ss, const long* ts, long so,
-                          long to, int acc, hipStream_t st);
-void fm_dot_interaction_fwd(const void* const* z, int F, long ldz, void* out, long ldo, long B, int D, int W, int self,
-                            hipStream_t s);
-void fm_dot_interaction_bwd(const void* const* z, int F, long ldz, const void* dout, long ldo, void* const* dz, long lddz,
-                            unsigned acc_mask, long B, int D, int self, hipStream_t s);
-void fm_dot_interaction_fwd_f32(const float* const* z, int F, long ldz, float* out, long ldo, long B, int D, int W, int self,
-                                hipStream_t s);
-void fm_dot_interaction_bwd_f32(const float* const* z, int F, long ldz, const float* dout, long ldo, float* const* dz,
-                                long lddz, unsigned acc_mask, long B, int D, int self, int act0, hipStream_t s);
-void fm_sgd_update(float* W, float* G, float* V, unsigned short* Wc, const float* lr, long n, float wd, float mom,
-                   int nesterov, int zero_g, hipStream_t s);
-void fm_adagrad_update(float* W, float* G, float* H, unsigned short* Wc, const float* lr, long n, float wd, float eps,
-                       int zero_g, hipStream_t s);
-void fm_adam_update(float* W, float* G, float* M, float* V, unsigned short* Wc, long n, const float* alpha_t,
-                    float b1, float b2, float wd, float eps, int zero_g, hipStream_t s);
-void fm_cast_bf16(const float* src, unsigned short* dst, long n, hipStream_t s);
-void fm_loss_fwd_bwd(const void* logits, int logits_bf16, const void* labels, void* grad, int grad_bf16, long B, int C,
-                     int loss_type, float scale, float* acc, int mask, float clamp_t, hipStream_t s);
-void fm_auc_hist_variant(const void* scores, int scores_bf16, const float* labels, long B, long long* hist, long long* invalid,
-                         int shift, int rounds, hipStream_t s);
-void fm_unary_forward(int code, const void* x, void* y, long n, int bf16, hipStream_t s);
-void fm_unary_backward(int code, const void* x, const void* y, const void* dy, void* dx, long n, int acc, int bf16,
-                       hipStream_t s);
-void fm_binary_forward(int code, const void* a, const void* b, void* y, long n, int relu, int bf16, hipStream_t s);
-void fm_binary_backward(int code, const void* a, const void* b, const void* dy, const void* ymask, void* da, void* db,
-                        long n, int acca, int accb, int bf16, hipStream_t s);
-void fm_act_bwd_bias(const void* y, const void* dy, void* dpre, float* db, long B, int N, int act, int bf16, hipStream_t s);
-void fm_cross_forward(const void* x0, const void* t, const void* x, void* y, long n, int bf16, hipStream_t s);
-void fm_cross_backward(const void* dy, const void* x0, const void* t, void* dt, void* dx0, void* dx, long n, int acct, int acc0,
-                       int accx, int self, int bf16, hipStream_t s);
-void fm_multi_copy2d(int n, const void* const* src, void* const* dst, const long* rows, const long* cols, const long* lds,
-                     const long* ldd, int add_mask, int elem_bytes, hipStream_t s);
-void fm_permute_nd(const void* x, void* y, int nd, const long* out_dims, const long* in_strides_perm, int acc, int bf16,
-                   hipStream_t s);
-void fm_reverse_axis(const void* x, void* y, long outer, long len, long inner, int acc, int bf16, hipStream_t s);
-void fm_softmax_fwd(const void* x, void* y, long rows, int C, int bf16, hipStream_t s);
-void fm_dropout_apply(const void* x, void* y, long n, float rate, unsigned seed, unsigned step, int acc, int bf16,
-                      hipStream_t s);
-void fm_im2col(const void* x, void* col, int N, int C, int H, int W, int R, int S, int P, int Q, int sh, int sw, int pt,
-               int pl, int ldcol, int bf16, hipStream_t st);
-void fm_col2im(const void* dcol, void* dx, int N, int C, int H, int W, int R, int S, int P, int Q, int sh, int sw, int pt,
-               int pl, int ldcol, int acc, int bf16, hipStream_t st);
-void fm_transpose_batched(const void* in, const void* yin, void* out, int N, int A, int B, int act, int mode, int bf16,
-                          hipStream_t st);
-void fm_pool_fwd(const void* x, void* y, unsigned char* code, int N, int C, int H, int W, int P, int Q, int kh, int kw, int sh,
-                 int sw, int pt, int pl, int is_max, int act, int bf16, hipStream_t st);
-void fm_pool_bwd(const void* x, const void* y, const void* dy, void* dx, unsigned char* code, int code_ready, int N, int C,
-                 int H, int W, int P, int Q, int kh, int kw, int sh, int sw, int pt, int pl, int is_max, int act, int acc,
-                 int bf16, hipStream_t st);
-void fm_pool_last_form(int* out);
-void fm_bn_fwd(const void* x, void* y, const float* gamma, const float* beta, float* stats, float* meaninv, int N, int C,
-               int HW, float eps, int relu, int bf16, hipStream_t st);
-void fm_bn_bwd(const void* x, const void* y, const void* dy, const float* meaninv, const float* gamma, float* gsum,
-               float* dgamma, float* dbeta, void* dx, int N, int C, int HW, int relu, int acc, int bf16, hipStream_t st);
-void fm_compact_rows(const float* src, float* dst, int K, int n, int ldp, int acc, hipStream_t st);
-int fm_conv_lda(int cols);
-int fm_conv_fwd(const void* x, const void* w, void* wpad, const float* bias, void* y, int bf16, int N, int C, int H, int W,
-                int K, int R, int S, int P, int Q, int sh, int sw, int pt, int pl, int act, hipStream_t s);
-int fm_conv_dgrad(const void* g, const void* w, void* wt, void* dx, int accum, int bf16, int N, int C, int H, int W, int K,
-                  int R, int S, int P, int Q, int sh, int sw, int pt, int pl, hipStream_t s);
-int fm_conv_wgrad(const void* g, const void* x, float* dw, int bf16, int N, int C, int H, int W, int K, int R, int S, int P,
-                  int Q, int sh, int sw, int pt, int pl, hipStream_t s);
-void fm_conv_act_bwd(const void* dy, const void* y, void* g, float* db, int bf16, int N, int K, int PQ, int act,
-                     hipStream_t s);
-void fm_conv_s2d_run(const void* x, void* xs, int bf16, int N, int C, int H, int W, int s, int pt, int pl, int Hs, int Ws,
-                     int inv, int acc, hipStream_t st);
-void fm_conv_w_s2d_run(const void* w, void* ws, const float* dws, float* dw, int bf16, int K, int C, int R, int S, int s,
-                       int Rs, int Ss, int inv, hipStream_t st);
-void fm_pad_rows(const void* src, void* dst, int K, int n, int ldp, int bf16, hipStream_t st);
-int fm_stem_supported(int C, int K, int R, int S, int sh, int sw);
-long fm_stem_wgrad_ws(int C, int K, int R, int S, int s);
-long fm_stem_wf_elems(int C, int K, int R, int S, int s);
-int fm_stem_fwd_run(const void* x, const void* w, void* wf, const float* bias, void* y, int N, int C, int H, int W, int R, int S,
-                    int P, int Q, int s, int pt, int pl, int act, hipStream_t st);
-int fm_stem_wgrad_run(const void* x, const void* y, const void* dy, float* dw, float* db, float* ws, int N, int C, int H,
-                      int W, int R, int S, int P, int Q, int s, int pt, int pl, int act, hipStream_t st);
-void fm_nhwc_stage_run(const void* src, void* dst, int N, int C, int H, int W, int Cp, int Hp, int Wp, int top, int left,
-                       int dh, int dw, hipStream_t s);
-void fm_nhwc_stage_grad_run(const void* dy, const void* y, void* dst, int act, int N, int C, int H, int W, int Cp, int Hp,
-                            int Wp, int top, int left, int dh, int dw, hipStream_t s);
-void fm_conv_nhwc_dgrad_strided(const void* gs, long gs_bytes, const void* w, void* wsub, void* dx, int accum, int N, int C,
-                                int H, int W, int K, int R, int S, int Kp, int Hg, int Wg, int gt, int gl, int sh, int sw,
-                                void* out2, int H2, int W2, int C2, int t2, int l2, int d2h, int d2w, int write_nchw,
-                                hipStream_t s);
-long fm_conv_nhwc_wgrad_ws(int N, int K, int P, int Q, int R, int S, int Cp);
-void fm_conv_nhwc_set_shape(int mode, int shape);
-void fm_cnhwc_wprep_multi_run(int n, const void* const* w, void* const* out, void* const* out2, const int* K, const int* C,
-                              const int* R, const int* S, const int* Cp, const int* Kp, hipStream_t s);
-void fm_cnhwc_wprep_run(const void* w, void* out, void* out2, const float* g2, float* dw, int K, int C, int R, int S, int Cp,
-                        int Kp, int mode, int nsplit, hipStream_t s);
-void fm_conv_nhwc_fwd(const void* xs, long xs_bytes, const void* wf, const float* bias, void* y, int N, int K, int P, int Q,
-                      int R, int S, int Cp, int Hp, int Wp, int sh, int sw, int act, void* out2, int H2, int W2, int C2, int t2,
-                      int l2, int d2h, int d2w, int write_nchw, hipStream_t s);
-void fm_conv_nhwc_dgrad(const void* gs, long gs_bytes, const void* wd, void* dx, int accum, int N, int C, int H, int W, int R,
-                        int S, int Kp, int Hg, int Wg, void* out2, int H2, int W2, int C2, int t2, int l2, int d2h, int d2w,
-                        int write_nchw, hipStream_t s);
-int fm_conv_nhwc_wgrad(const void* gs, long gs_bytes, const void* xs, long xs_bytes, float* g2, float* db, int N, int K, int Kp, int P,
-                        int Q, int Hg, int Wg, int gt, int gl, int gsh, int gsw, int R, int S, int Cp, int Hp, int Wp, int sh,
-                        int sw, int* ptab, int build_tab, hipStream_t s);
-void fm_lstm_init(const void* h0, const void* c0, void* hprev, long ldhp, float* cinit, int B, int H, int bf16, hipStream_t s);
-void fm_lstm_cell_fwd(float* G, long ldg, const float* c_prev, long ldcp, float* c_out, long ldc, void* y, long ldy,
-                      void* hprev_next, long ldhp, void* hT, void* cT, int B, int H, int bf16, hipStream_t s);
-void fm_lstm_cell_bwd(const float* A, long lda, const float* c_t, long ldc, const float* c_prev, long ldcp,
-                      const void* dy, long ldy, const float* dh, float* dc, void* dG, long lddg, int B, int H, int bf16,
-                      hipStream_t s);
-}
 
 namespace {
 
 hipStream_t cur() { return at::hip::getCurrentHIPStream().stream(); }
 
-const void* cptr(const c10::optional<torch::Tensor>& t) { return (t.has_value() && t->defined()) ? t->data_ptr() : nullptr; }
-void* mptr(const c10::optional<torch::Tensor>& t) { return (t.has_value() && t->defined()) ? t->data_ptr() : nullptr; }
+// optional tensors: given = passed and defined; the pointer helpers give nullptr otherwise (fptr
+// keeps data_ptr<float>()'s dtype check)
+bool given(const c10::optional<torch::Tensor>& t) { return t.has_value() && t->defined(); }
+const void* cptr(const c10::optional<torch::Tensor>& t) { return given(t) ? t->data_ptr() : nullptr; }
+void* mptr(const c10::optional<torch::Tensor>& t) { return given(t) ? t->data_ptr() : nullptr; }
+float* fptr(const c10::optional<torch::Tensor>& t) { return given(t) ? t->data_ptr<float>() : nullptr; }
 
 void check_cuda(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a HIP device tensor");
@@ -217,8 +41,8 @@ void check_update(const char* op, const torch::Tensor& W, const torch::Tensor& G
   TORCH_CHECK(W.is_cuda() && like_w(W, torch::kFloat32) && like_w(G, torch::kFloat32), op,
               ": W and G must be contiguous fp32 tensors of one size on one GPU");
   for (const auto& s : states)
-    TORCH_CHECK(!s.has_value() || !s->defined() || like_w(*s, torch::kFloat32), op, ": contiguous fp32 state of W's size");
-  TORCH_CHECK(!Wc.has_value() || !Wc->defined() || like_w(*Wc, torch::kBFloat16), op, ": contiguous bf16 mirror of W's size");
+    TORCH_CHECK(!given(s) || like_w(*s, torch::kFloat32), op, ": contiguous fp32 state of W's size");
+  TORCH_CHECK(!given(Wc) || like_w(*Wc, torch::kBFloat16), op, ": contiguous bf16 mirror of W's size");
   TORCH_CHECK(step.scalar_type() == torch::kFloat32 && step.numel() >= 1 && step.device() == W.device(), op,
               ": the step size must be an fp32 scalar on W's GPU");
 }
@@ -248,37 +72,37 @@ int gemm(torch::Tensor A, int64_t lda, int64_t sA, bool a_kcontig, torch::Tensor
     TORCH_CHECK(lastB + (batch - 1) * sB < B.numel(), "gemm: B too small");
   }
   TORCH_CHECK((M - 1) * ldc + (N - 1) + (batch - 1) * sC < C.numel(), "gemm: C too small");
-  if (bias.has_value() && bias->defined()) {
+  if (given(bias)) {
     TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->numel() >= N, "bias must be fp32 [N]");
   }
-  if (act_y.has_value() && act_y->defined()) {
+  if (given(act_y)) {
     TORCH_CHECK(act_y->scalar_type() == A.scalar_type() && batch == 1 && (M - 1) * lday + N <= act_y->numel(),
                 "gemm act_y: [M, >=N] of the operand dtype");
   }
-  if (rowsum_a.has_value() && rowsum_a->defined()) {
+  if (given(rowsum_a)) {
     TORCH_CHECK(!a_kcontig && rowsum_a->scalar_type() == torch::kFloat32 && rowsum_a->numel() >= M && batch == 1,
                 "gemm rowsum_a: fp32 [M], MN-contiguous A");
   }
-  if (colsum.has_value() && colsum->defined()) {
+  if (given(colsum)) {
     TORCH_CHECK(colsum->scalar_type() == torch::kFloat32 && colsum->numel() >= N && batch == 1, "gemm colsum: fp32 [N]");
   }
   float* w = nullptr;
   long wsb = 0;
-  if (ws.has_value() && ws->defined()) {
+  if (given(ws)) {
     w = ws->data_ptr<float>();
     wsb = ws->numel() * 4;
   }
   int ks;
   if (f32)
     ks = fm_gemm_f32(A.data_ptr<float>(), lda, sA, a_kcontig, B.data_ptr<float>(), ldb, sB, b_kcontig, C.data_ptr<float>(),
-                     ldc, sC, bias.has_value() && bias->defined() ? bias->data_ptr<float>() : nullptr, (int)M, (int)N,
-                     (int)K, (int)batch, (float)alpha, beta ? 1 : 0, (int)act, w, wsb, (int)ksplit,
-                     (const float*)cptr(act_y), lday, (int)bwd_act, (float*)mptr(colsum), (float*)mptr(rowsum_a), cur());
+                     ldc, sC, fptr(bias), (int)M, (int)N, (int)K, (int)batch, (float)alpha, beta ? 1 : 0, (int)act, w, wsb,
+                     (int)ksplit, (const float*)cptr(act_y), lday, (int)bwd_act, (float*)mptr(colsum),
+                     (float*)mptr(rowsum_a), cur());
   else
     ks = fm_gemm(A.data_ptr(), lda, sA, a_kcontig, B.data_ptr(), ldb, sB, b_kcontig, C.data_ptr(), ldc, sC,
-                 C.scalar_type() == torch::kFloat32, bias.has_value() && bias->defined() ? bias->data_ptr<float>() : nullptr,
-                 (int)M, (int)N, (int)K, (int)batch, (float)alpha, beta ? 1 : 0, (int)act, w, wsb, (int)ksplit,
-                 cptr(act_y), lday, (int)bwd_act, (float*)mptr(colsum), (float*)mptr(rowsum_a), cur());
+                 C.scalar_type() == torch::kFloat32, fptr(bias), (int)M, (int)N, (int)K, (int)batch, (float)alpha,
+                 beta ? 1 : 0, (int)act, w, wsb, (int)ksplit, cptr(act_y), lday, (int)bwd_act, (float*)mptr(colsum),
+                 (float*)mptr(rowsum_a), cur());
   return ks;
 }
 
@@ -311,7 +135,7 @@ std::vector<int64_t> gemm_f32_grouped(std::vector<torch::Tensor> A, std::vector<
     TORCH_CHECK(lastA < A[i].numel() && lastB < B[i].numel(), "gemm_f32_grouped: operand too small");
     TORCH_CHECK((M[i] - 1) * ldc[i] + (N[i] - 1) < C[i].numel(), "gemm_f32_grouped: C too small");
     float* rs = nullptr;
-    if (rowsum_a[i].has_value() && rowsum_a[i]->defined()) {
+    if (given(rowsum_a[i])) {
       TORCH_CHECK(!a_kcontig && rowsum_a[i]->scalar_type() == torch::kFloat32 && rowsum_a[i]->numel() >= M[i] &&
                       rowsum_a[i]->is_cuda(), "gemm_f32_grouped rowsum_a: fp32 [M], MN-contiguous A");
       rs = rowsum_a[i]->data_ptr<float>();
@@ -331,7 +155,7 @@ void sgd_segs(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, 
               bool zero_g) {
   TORCH_CHECK(off.size() == len.size(), "sgd_segs: off/len");
   check_update("sgd_segs", W, G, {V}, Wc, lr);
-  TORCH_CHECK(mom <= 0.0 || (V.has_value() && V->defined()), "sgd_segs: momentum buffer");
+  TORCH_CHECK(mom <= 0.0 || given(V), "sgd_segs: momentum buffer");
   for (size_t i = 0; i < off.size(); ++i)
     TORCH_CHECK(off[i] >= 0 && len[i] >= 0 && off[i] + len[i] <= W.numel(), "sgd_segs: range outside the buffer");
   // the kernel's vector body assumes the flat buffers start 16-B aligned (8-B for the bf16 mirror)
@@ -359,13 +183,13 @@ int gemm_dw_sgd(torch::Tensor dpre, torch::Tensor x, torch::Tensor W, c10::optio
                   dpre.stride(1) == 1 && x.stride(1) == 1,
               "gemm_dw_sgd: dpre [B, out], x [B, in] (both bf16 or both fp32), unit column stride");
   TORCH_CHECK(W.scalar_type() == torch::kFloat32 && W.is_contiguous() && W.numel() == Nout * Kin, "gemm_dw_sgd: W [out, in] fp32");
-  if (Wc.has_value() && Wc->defined())
+  if (given(Wc))
     TORCH_CHECK(Wc->scalar_type() == torch::kBFloat16 && Wc->is_contiguous() && Wc->numel() == W.numel(), "gemm_dw_sgd: Wc");
-  if (V.has_value() && V->defined())
+  if (given(V))
     TORCH_CHECK(V->scalar_type() == torch::kFloat32 && V->is_contiguous() && V->numel() == W.numel(), "gemm_dw_sgd: V");
-  TORCH_CHECK(mom <= 0.0 || (V.has_value() && V->defined()), "gemm_dw_sgd: momentum needs V");
+  TORCH_CHECK(mom <= 0.0 || given(V), "gemm_dw_sgd: momentum needs V");
   TORCH_CHECK(lr.scalar_type() == torch::kFloat32 && lr.numel() >= 1 && lr.is_cuda(), "gemm_dw_sgd: lr device fp32 scalar");
-  if (db.has_value() && db->defined())
+  if (given(db))
     TORCH_CHECK(db->scalar_type() == torch::kFloat32 && db->numel() >= Nout, "gemm_dw_sgd: db fp32 [out]");
   TORCH_CHECK((B - 1) * dpre.stride(0) + Nout <= dpre.numel() && (B - 1) * x.stride(0) + Kin <= x.numel(), "gemm_dw_sgd: extents");
   if (f32)
@@ -390,7 +214,7 @@ bool smallk_fwd(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2 && w.is_contiguous() && x.stride(1) == 1 && y.stride(1) == 1 &&
                   w.size(1) == x.size(1) && y.size(0) == x.size(0) && y.size(1) == w.size(0),
               "smallk_fwd: x [M, K], w [N, K], y [M, N]");
-  if (bias.has_value() && bias->defined())
+  if (given(bias))
     TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->numel() == w.size(0), "smallk_fwd: bias [N] fp32");
   return fm_smallk_fwd_launch(x.data_ptr(), x.stride(0), w.data_ptr(), (const float*)mptr(bias), y.data_ptr(), y.stride(0),
                               x.size(0), (int)x.size(1), (int)w.size(0), (int)act, bf ? 1 : 0, cur()) == 0;
@@ -409,13 +233,13 @@ bool smallk_dw(torch::Tensor dpre, torch::Tensor x, torch::Tensor dw, c10::optio
   const int64_t M = dpre.size(0), N = dpre.size(1), K = x.size(1);
   TORCH_CHECK(x.size(0) == M && dpre.stride(1) == 1 && x.stride(1) == 1 && dw.is_contiguous() && dw.numel() == N * K,
               "smallk_dw: dpre [M, N], x [M, K], dw [N, K]");
-  if (db.has_value() && db->defined()) TORCH_CHECK(db->scalar_type() == torch::kFloat32 && db->numel() >= N, "smallk_dw: db");
-  const bool upd = lr.has_value() && lr->defined();
+  if (given(db)) TORCH_CHECK(db->scalar_type() == torch::kFloat32 && db->numel() >= N, "smallk_dw: db");
+  const bool upd = given(lr);
   if (upd) {
     TORCH_CHECK(lr->scalar_type() == torch::kFloat32 && lr->is_cuda(), "smallk_dw: lr device fp32 scalar");
-    TORCH_CHECK(mom <= 0.0 || (V.has_value() && V->defined()), "smallk_dw: momentum needs V");
-    if (V.has_value() && V->defined()) TORCH_CHECK(V->is_contiguous() && V->numel() == dw.numel(), "smallk_dw: V");
-    if (Wc.has_value() && Wc->defined())
+    TORCH_CHECK(mom <= 0.0 || given(V), "smallk_dw: momentum needs V");
+    if (given(V)) TORCH_CHECK(V->is_contiguous() && V->numel() == dw.numel(), "smallk_dw: V");
+    if (given(Wc))
       TORCH_CHECK(Wc->scalar_type() == torch::kBFloat16 && Wc->is_contiguous() && Wc->numel() == dw.numel(), "smallk_dw: Wc");
   }
   return fm_smallk_dw_launch(dpre.data_ptr(), dpre.stride(0), x.data_ptr(), x.stride(0), dw.data_ptr<float>(),
@@ -429,20 +253,19 @@ void skinny_fwd(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b
   TORCH_CHECK(w.numel() == x.size(1) && y.size(1) == 1 && x.stride(1) == 1, "skinny_fwd: x[B,K] w[1,K] y[B,1]");
   TORCH_CHECK(x.scalar_type() == w.scalar_type() && x.scalar_type() == y.scalar_type(), "skinny_fwd: one dtype");
   if (x.scalar_type() == torch::kFloat32) {
-    fm_skinny_fwd_f32_launch(x.data_ptr<float>(), x.stride(0), w.data_ptr<float>(),
-                             bias.has_value() && bias->defined() ? bias->data_ptr<float>() : nullptr, y.data_ptr<float>(),
+    fm_skinny_fwd_f32_launch(x.data_ptr<float>(), x.stride(0), w.data_ptr<float>(), fptr(bias), y.data_ptr<float>(),
                              y.stride(0), x.size(0), (int)x.size(1), (int)act, cur());
     return;
   }
-  fm_skinny_fwd(x.data_ptr(), x.stride(0), w.data_ptr(), bias.has_value() && bias->defined() ? bias->data_ptr<float>() : nullptr,
-                y.data_ptr(), y.stride(0), x.size(0), (int)x.size(1), (int)act, cur());
+  fm_skinny_fwd(x.data_ptr(), x.stride(0), w.data_ptr(), fptr(bias), y.data_ptr(), y.stride(0), x.size(0),
+                (int)x.size(1), (int)act, cur());
 }
 
 void skinny_bwd(torch::Tensor x, torch::Tensor w, torch::Tensor y, torch::Tensor dy, c10::optional<torch::Tensor> dx, bool dx_acc,
                 torch::Tensor dw, c10::optional<torch::Tensor> db, int64_t act, int64_t bact) {
   // bact: activation backward of the layer below (output x) fused into dX; 10 = none
   TORCH_CHECK(w.numel() == x.size(1) && dw.numel() == x.size(1), "skinny_bwd: shapes");
-  long lddx = (dx.has_value() && dx->defined()) ? dx->stride(0) : 0;
+  long lddx = given(dx) ? dx->stride(0) : 0;
   if (x.scalar_type() == torch::kFloat32) {
     TORCH_CHECK(w.scalar_type() == torch::kFloat32 && y.scalar_type() == torch::kFloat32 && dy.scalar_type() == torch::kFloat32,
                 "skinny_bwd: fp32 operands");
@@ -489,8 +312,7 @@ void embedding_bwd(torch::Tensor idx, torch::Tensor dy, int64_t ldg, torch::Tens
   long B = idx.size(0);
   int bag = idx.size(1);
   fm_embedding_bwd(idx.data_ptr(), idx.scalar_type() == torch::kInt64, dy.data_ptr(), is_bf16(dy), W.data_ptr<float>(),
-                   lr.has_value() && lr->defined() ? lr->data_ptr<float>() : nullptr, B, bag, (int)W.size(0),
-                   (int)W.size(1), ldg, (float)scale, cur());
+                   fptr(lr), B, bag, (int)W.size(0), (int)W.size(1), ldg, (float)scale, cur());
 }
 
 struct TabArgs {
@@ -566,7 +388,7 @@ void embedding_bwd_multi(std::vector<torch::Tensor> W, std::vector<torch::Tensor
     TORCH_CHECK(claim->size() == 3 * W.size(), "claim: 3 buffers per table");
     for (size_t k = 0; k < W.size(); ++k) {
       const auto& o = (*claim)[3 * k];
-      if (!o.has_value() || !o->defined()) continue;
+      if (!given(o)) continue;
       const auto& d = (*claim)[3 * k + 1];
       const auto& c = (*claim)[3 * k + 2];
       TORCH_CHECK(o->scalar_type() == torch::kInt32 && o->numel() >= W[k].size(0), "claim owner: int32 [rows]");
@@ -579,8 +401,7 @@ void embedding_bwd_multi(std::vector<torch::Tensor> W, std::vector<torch::Tensor
     }
   }
   fm_embedding_bwd_multi((int)W.size(), a.Wm.data(), a.idx.data(), a.idx64.data(), a.cact.data(), a.ld.data(), lo.data(),
-                         a.rows.data(), a.D.data(), a.bag.data(), a.scale.data(), is_bf16(dy[0]),
-                         lr.has_value() && lr->defined() ? lr->data_ptr<float>() : nullptr, a.B,
+                         a.rows.data(), a.D.data(), a.bag.data(), a.scale.data(), is_bf16(dy[0]), fptr(lr), a.B,
                          any ? own.data() : nullptr, any ? dup.data() : nullptr, any ? nd.data() : nullptr, cur());
 }
 
@@ -891,7 +712,7 @@ void dot_bwd(std::vector<torch::Tensor> zs, int64_t ldz, torch::Tensor dout, int
 void sgd(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, c10::optional<torch::Tensor> Wc, torch::Tensor lr,
          double wd, double mom, bool nesterov, bool zero_grad) {
   check_update("sgd", W, G, {V}, Wc, lr);
-  TORCH_CHECK(mom <= 0.0 || (V.has_value() && V->defined()), "sgd: momentum buffer");
+  TORCH_CHECK(mom <= 0.0 || given(V), "sgd: momentum buffer");
   fm_sgd_update(W.data_ptr<float>(), G.data_ptr<float>(), (float*)mptr(V), (unsigned short*)mptr(Wc), lr.data_ptr<float>(),
                 W.numel(), (float)wd, (float)mom, nesterov ? 1 : 0, zero_grad ? 1 : 0, cur());
 }
@@ -916,7 +737,7 @@ void loss(int64_t loss_type, torch::Tensor logits, torch::Tensor labels, c10::op
           torch::Tensor acc, int64_t mask, double clamp_t) {
   long B = logits.size(0);
   int C = (int)(logits.numel() / std::max<long>(1, B));
-  int gb = (grad.has_value() && grad->defined()) ? is_bf16(*grad) : 0;
+  int gb = given(grad) ? is_bf16(*grad) : 0;
   fm_loss_fwd_bwd(logits.data_ptr(), is_bf16(logits), labels.data_ptr(), mptr(grad), gb, B, C, (int)loss_type, (float)scale,
                   acc.data_ptr<float>(), (int)mask, (float)clamp_t, cur());
 }
@@ -952,7 +773,7 @@ void binary_fwd(int64_t code, torch::Tensor a, torch::Tensor b, torch::Tensor y,
 void binary_bwd(int64_t code, torch::Tensor a, torch::Tensor b, torch::Tensor dy, c10::optional<torch::Tensor> ymask,
                 c10::optional<torch::Tensor> da, c10::optional<torch::Tensor> db, bool acca, bool accb) {
   TORCH_CHECK(dy.numel() == a.numel() && dy.numel() == b.numel() && dy.scalar_type() == a.scalar_type(), "binary_bwd: operands");
-  if (ymask.has_value() && ymask->defined())
+  if (given(ymask))
     TORCH_CHECK(ymask->numel() == dy.numel() && ymask->scalar_type() == dy.scalar_type(), "binary_bwd: ymask");
   fm_binary_backward((int)code, a.data_ptr(), b.data_ptr(), dy.data_ptr(), cptr(ymask), mptr(da), mptr(db), a.numel(), acca,
                      accb, is_bf16(a), cur());
@@ -960,7 +781,7 @@ void binary_bwd(int64_t code, torch::Tensor a, torch::Tensor b, torch::Tensor dy
 // DCNv2 cross combine (cross.hip).  The kernels index every operand as a flat array of ref's length:
 // each one given must be a contiguous device tensor of ref's dtype and element count
 static void cross_operand(const torch::Tensor& ref, const c10::optional<torch::Tensor>& t, const char* what) {
-  if (!t.has_value() || !t->defined()) return;
+  if (!given(t)) return;
   TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == ref.scalar_type() && t->numel() == ref.numel(), what,
               ": contiguous device tensor of the first operand's dtype and size expected");
 }
@@ -993,7 +814,7 @@ void act_bwd_bias(torch::Tensor y, torch::Tensor dy, c10::optional<torch::Tensor
                   int64_t B, int64_t N, int64_t act) {
   TORCH_CHECK(y.scalar_type() == dy.scalar_type() && (y.scalar_type() == torch::kBFloat16 || y.scalar_type() == torch::kFloat32),
               "act_bwd_bias: bf16 or fp32");
-  if (dpre.has_value() && dpre->defined()) TORCH_CHECK(dpre->scalar_type() == y.scalar_type(), "act_bwd_bias: dpre dtype");
+  if (given(dpre)) TORCH_CHECK(dpre->scalar_type() == y.scalar_type(), "act_bwd_bias: dpre dtype");
   fm_act_bwd_bias(y.data_ptr(), dy.data_ptr(), mptr(dpre), (float*)mptr(db), B, (int)N, (int)act, is_bf16(y), cur());
 }
 // uint8 [N][H][W][3] decoded RGB -> normalized [N][3][H][W] fp32 / bf16 (image.hip)
@@ -1119,7 +940,7 @@ void conv_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor wpad, c10::optiona
   TORCH_CHECK(wpad.numel() >= conv_scratch(w.size(0), w.size(1) * w.size(2) * w.size(3)) &&
                   ((uintptr_t)wpad.data_ptr() & 15) == 0, "conv_fwd: wpad scratch too small");
   const float* b = nullptr;
-  if (bias.has_value() && bias->defined()) {
+  if (given(bias)) {
     TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->numel() == w.size(0), "conv_fwd: fp32 bias[K]");
     b = bias->data_ptr<float>();
   }
@@ -1165,7 +986,7 @@ void stem_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor wf, c10::optional<
   TORCH_CHECK(is_bf16(x), "stem_fwd: bf16 operands");
   TORCH_CHECK(stem_supported(x.size(1), w.size(0), w.size(2), w.size(3), s, s), "stem_fwd: unsupported geometry");
   const float* b = nullptr;
-  if (bias.has_value() && bias->defined()) {
+  if (given(bias)) {
     TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->numel() == w.size(0) && bias->is_contiguous(),
                 "stem_fwd: fp32 bias[K]");
     b = bias->data_ptr<float>();
@@ -1190,7 +1011,7 @@ void stem_wgrad(torch::Tensor x, torch::Tensor y, torch::Tensor dy, torch::Tenso
   TORCH_CHECK(dw.scalar_type() == torch::kFloat32 && dw.is_contiguous() && dw.numel() == y.size(1) * x.size(1) * R * S,
               "stem_wgrad: contiguous fp32 dw[K*C*R*S]");
   float* dbp = nullptr;
-  if (db.has_value() && db->defined()) {
+  if (given(db)) {
     TORCH_CHECK(db->scalar_type() == torch::kFloat32 && db->is_contiguous() && db->numel() == y.size(1), "stem_wgrad: fp32 db[K]");
     dbp = db->data_ptr<float>();
   }
@@ -1326,7 +1147,7 @@ void cnhwc_wprep_multi(std::vector<torch::Tensor> w, std::vector<torch::Tensor> 
 // d2h, d2w, write_nchw}); every position the epilogue can address lies inside it
 static void* out2_chk(const c10::optional<torch::Tensor>& out2, const std::vector<int64_t>& o2, long N, long M, long OH,
                       long OW) {
-  if (!out2.has_value() || !out2->defined()) return nullptr;
+  if (!given(out2)) return nullptr;
   TORCH_CHECK(o2.size() == 8, "out2 geometry: {H2, W2, C2, t2, l2, d2h, d2w, write_nchw}");
   TORCH_CHECK(o2[2] >= M && o2[5] >= 1 && o2[6] >= 1, "out2: C2 >= channels, dilation >= 1");
   nhwc_chk(*out2, N * o2[0] * o2[1] * o2[2], "out2");
@@ -1343,7 +1164,7 @@ void conv_nhwc_fwd(torch::Tensor xs, torch::Tensor wf, c10::optional<torch::Tens
   nhwc_chk(wf, K * R * S * Cp, "conv_nhwc_fwd wf");
   nhwc_chk(y, N * K * P * Q, "conv_nhwc_fwd y");
   const float* b = nullptr;
-  if (bias.has_value() && bias->defined()) {
+  if (given(bias)) {
     TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->numel() == K && bias->is_cuda(), "conv_nhwc_fwd: fp32 bias[K]");
     b = bias->data_ptr<float>();
   }
@@ -1404,7 +1225,7 @@ int64_t conv_nhwc_wgrad(torch::Tensor gs, torch::Tensor xs, torch::Tensor g2, c1
                   g2.numel() >= fm_conv_nhwc_wgrad_ws((int)N, (int)K, (int)P, (int)Q, (int)R, (int)S, (int)Cp),
               "conv_nhwc_wgrad: fp32 g2 slabs (conv_nhwc_wgrad_ws floats)");
   float* dbp = nullptr;
-  if (db.has_value() && db->defined()) {
+  if (given(db)) {
     TORCH_CHECK(db->is_cuda() && db->scalar_type() == torch::kFloat32 && db->numel() == K && db->is_contiguous(),
                 "conv_nhwc_wgrad: fp32 db[K]");
     dbp = db->data_ptr<float>();
@@ -1425,7 +1246,7 @@ void conv_act_bwd(torch::Tensor dy, torch::Tensor y, torch::Tensor g, c10::optio
   same_dt(dy, g, "conv_act_bwd");
   TORCH_CHECK(dy.dim() == 4 && y.sizes() == dy.sizes() && g.sizes() == dy.sizes(), "conv_act_bwd: [N,K,P,Q]");
   float* dbp = nullptr;
-  if (db.has_value() && db->defined()) {
+  if (given(db)) {
     TORCH_CHECK(db->scalar_type() == torch::kFloat32 && db->numel() == dy.size(1), "conv_act_bwd: fp32 db[K]");
     dbp = db->data_ptr<float>();
   }
@@ -1433,7 +1254,7 @@ void conv_act_bwd(torch::Tensor dy, torch::Tensor y, torch::Tensor g, c10::optio
                   (int)(dy.size(2) * dy.size(3)), (int)act, cur());
 }
 static unsigned char* code_ptr(const c10::optional<torch::Tensor>& code, const torch::Tensor& y, const char* n) {
-  if (!code.has_value() || !code->defined()) return nullptr;
+  if (!given(code)) return nullptr;
   check_cuda(*code, n);
   TORCH_CHECK(code->scalar_type() == torch::kUInt8 && code->numel() >= y.numel(), n, ": uint8 code[y.numel()]");
   return code->data_ptr<uint8_t>();
@@ -1484,7 +1305,7 @@ void bn_bwd(torch::Tensor x, torch::Tensor y, torch::Tensor dy, torch::Tensor me
   chk4(dy, "dy");
   same_dt(x, dy, "bn_bwd");
   same_dt(x, y, "bn_bwd");
-  if (dx.has_value() && dx->defined()) same_dt(x, *dx, "bn_bwd");
+  if (given(dx)) same_dt(x, *dx, "bn_bwd");
   const long C = x.size(1);
   TORCH_CHECK(gsum.numel() >= 2 * C && dgamma.numel() >= C && dbeta.numel() >= C, "bn_bwd: sizes");
   fm_bn_bwd(x.data_ptr(), y.data_ptr(), dy.data_ptr(), meaninv.data_ptr<float>(), gamma.data_ptr<float>(),
@@ -1533,7 +1354,7 @@ void lstm_cell_bwd(torch::Tensor A, int64_t a_off, int64_t lda, torch::Tensor ct
   TORCH_CHECK(a_off + (B - 1) * lda + 4 * H <= A.numel() && dg_off + (B - 1) * lddg + 4 * H <= dG.numel() &&
                   dh.numel() >= B * H && dc.numel() >= B * H, "lstm_cell_bwd: extents");
   const void* dyp = nullptr;
-  if (dy.has_value() && dy->defined()) {
+  if (given(dy)) {
     TORCH_CHECK(dy_off + (B - 1) * ldy + H <= dy->numel() && dy->scalar_type() == dG.scalar_type(), "lstm_cell_bwd: dy extent");
     dyp = (const char*)dy->data_ptr() + dy->element_size() * dy_off;
   }

@@ -75,8 +75,3 @@ extern "C" void fm_auc_hist_variant(const void* scores, int scores_bf16, const f
   else
     hipLaunchKernelGGL(fm_auc_hist_kernel<float>, g, dim3(256), 0, s, (const float*)scores, labels, B, h, iv, shift, rounds);
 }
-
-extern "C" void fm_auc_hist(const void* scores, int scores_bf16, const float* labels, long B,
-                            long long* hist /*[2][1<<(32-shift)]*/, long long* invalid, int shift, hipStream_t s) {
-  fm_auc_hist_variant(scores, scores_bf16, labels, B, hist, invalid, shift, FM_AUC_PEEL_ROUNDS, s);
-}

@@ -4,6 +4,8 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
+#include "launchers.h"   // every extern "C" launcher definition is checked against its one declaration
+
 #define FM_HOST_DEVICE __host__ __device__ __forceinline__
 #define FM_DEVICE __device__ __forceinline__
 

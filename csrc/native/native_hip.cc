@@ -36,65 +36,7 @@
 #include <vector>
 
 #include "native_model.h"
-
-extern "C" {
-int fm_gemm_f32(const float* A, long lda, long sA, int a_kcontig, const float* B, long ldb, long sB, int b_kcontig, float* C,
-                long ldc, long sC, const float* bias, int M, int N, int K, int batch, float alpha, int beta, int act, float* ws,
-                long ws_bytes, int ksplit_req, const float* act_y, long lday, int bwd_act, float* colsum, float* rowsum_a,
-                hipStream_t stream);
-void fm_skinny_fwd_f32_launch(const float* x, long ldx, const float* w, const float* bias, float* y, long ldy, long B, int K,
-                              int act, hipStream_t s);
-void fm_skinny_bwd_f32_launch(const float* x, long ldx, const float* w, const float* y, long ldy, const float* dy, long lddy,
-                              float* dx, long lddx, int dx_acc, float* dw, float* db, long B, int K, int act, int bact,
-                              hipStream_t s);
-void fm_act_bwd_bias(const void* y, const void* dy, void* dpre, float* db, long B, int N, int act, int bf16, hipStream_t s);
-void fm_softmax_fwd(const void* x, void* y, long rows, int C, int bf16, hipStream_t s);
-void fm_loss_fwd_bwd(const void* logits, int logits_bf16, const void* labels, void* grad, int grad_bf16, long B, int C,
-                     int loss_type, float scale, float* acc, int mask, float clamp_t, hipStream_t s);
-void fm_sgd_update(float* W, float* G, float* V, unsigned short* Wc, const float* lr, long n, float wd, float mom, int nesterov,
-                   int zero_g, hipStream_t s);
-int fm_smallk_fwd_launch(const void* x, long ldx, const void* w, const float* bias, void* y, long ldy, long M, int K, int N,
-                         int act, int bf16, hipStream_t s);
-int fm_smallk_dw_launch(const void* dpre, long ldd, const void* x, long ldx, float* dw, float* db, long M, int K, int N,
-                        float* ws, long ws_bytes, float* V, unsigned short* Wc, const float* lr, float wd, float mom,
-                        int nesterov, int bf16, hipStream_t s);
-void fm_adam_update(float* W, float* G, float* M, float* V, unsigned short* Wc, long n, const float* alpha_t, float b1, float b2,
-                    float wd, float eps, int zero_g, hipStream_t s);
-void fm_embedding_fwd_multi(int n, const float* const* W, const void* const* idx, const int* idx64, void* const* out,
-                            const long* ldo, const long* lo, const int* rows, const int* D, const int* bag,
-                            const float* scale, int out_bf16, long B, hipStream_t st);
-void fm_embedding_bwd_multi(int n, float* const* W, const void* const* idx, const int* idx64, const void* const* dy,
-                            const long* ldg, const long* lo, const int* rows, const int* D, const int* bag,
-                            const float* scale, int dy_bf16, const float* lr, long B, int* const* owner,
-                            int* const* dups, int* const* ndup, hipStream_t st);
-void fm_binary_forward(int code, const void* a, const void* b, void* y, long n, int relu, int bf16, hipStream_t s);
-void fm_embedding_fwd(const void* idx, int idx64, const float* W, void* out, int out_bf16, long B, int bag, int rows, int D,
-                      long ldo, float scale, hipStream_t s);
-void fm_embedding_bwd(const void* idx, int idx64, const void* dy, int dy_bf16, float* W, const float* lr, long B, int bag,
-                      int rows, int D, long ldg, float scale, hipStream_t s);
-void fm_dot_interaction_fwd_f32(const float* const* z, int F, long ldz, float* out, long ldo, long B, int D, int W, int self,
-                                hipStream_t s);
-void fm_dot_interaction_bwd_f32(const float* const* z, int F, long ldz, const float* dout, long ldo, float* const* dz,
-                                long lddz, unsigned acc_mask, long B, int D, int self, int act0, hipStream_t s);
-int fm_conv_lda(int cols);
-int fm_conv_fwd(const void* x, const void* w, void* wpad, const float* bias, void* y, int bf16, int N, int C, int H, int W,
-                int K, int R, int S, int P, int Q, int sh, int sw, int pt, int pl, int act, hipStream_t s);
-int fm_conv_dgrad(const void* g, const void* w, void* wt, void* dx, int accum, int bf16, int N, int C, int H, int W, int K,
-                  int R, int S, int P, int Q, int sh, int sw, int pt, int pl, hipStream_t s);
-int fm_conv_wgrad(const void* g, const void* x, float* dw, int bf16, int N, int C, int H, int W, int K, int R, int S, int P,
-                  int Q, int sh, int sw, int pt, int pl, hipStream_t s);
-void fm_conv_act_bwd(const void* dy, const void* y, void* g, float* db, int bf16, int N, int K, int PQ, int act,
-                     hipStream_t s);
-void fm_pool_fwd(const void* x, void* y, unsigned char* code, int N, int C, int H, int W, int P, int Q, int kh, int kw,
-                 int sh, int sw, int pt, int pl, int is_max, int act, int bf16, hipStream_t st);
-void fm_pool_bwd(const void* x, const void* y, const void* dy, void* dx, unsigned char* code, int code_ready, int N, int C,
-                 int H, int W, int P, int Q, int kh, int kw, int sh, int sw, int pt, int pl, int is_max, int act, int acc,
-                 int bf16, hipStream_t st);
-void fm_bn_fwd(const void* x, void* y, const float* gamma, const float* beta, float* stats, float* meaninv, int N, int C,
-               int HW, float eps, int relu, int bf16, hipStream_t st);
-void fm_bn_bwd(const void* x, const void* y, const void* dy, const float* meaninv, const float* gamma, float* gsum,
-               float* dgamma, float* dbeta, void* dx, int N, int C, int HW, int relu, int acc, int bf16, hipStream_t st);
-}
+#include "../kernels/launchers.h"
 
 namespace flexmi {
 namespace nm {
