@@ -1402,8 +1402,6 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_set_dma", [](int on) { fm_gemm_set_dma(on); });
   m.def("gemm_dma_enabled", []() { return fm_gemm_dma_enabled(); });
   m.def("gemm_f32_get_split", []() { return fm_gemm_f32_get_split(); });
-  // sparse-SGD kernels of tables with slot buffers: 1 = count / update, 0 = claim / dup / owner
-  m.def("embedding_set_bwd_mode", [](bool count) { fm_embedding_set_bwd_mode(count ? 1 : 0); });
   // forward kernel of a launch set: 0 = auto (balanced for vectorisable sets of unequal bags), 1 = never
   // balanced, 2 = balanced for every vectorisable set
   m.def("embedding_set_fwd_mode", [](int mode) { fm_embedding_set_fwd_mode(mode); });

@@ -11,10 +11,15 @@
 //
 // Forward: lane = 4 consecutive columns of one sample (D/4 lanes per row: a 512-B fp32 row of a
 // D=128 table is read by 32 lanes with 16-B loads), sum over the bag, bf16/fp32 output written
-// with 8/16-B stores straight into the consumer's buffer (row stride ldo).  Tables of one bag size
-// get the same grid each (blockIdx.y = table); tables of unequal bag sizes (per-table multi-hot sizes)
-// share a one-dimensional grid dealt out by lookups -- "work-balanced forward" below.
+// with 8/16-B stores straight into the consumer's buffer (row stride ldo).  Five forms
+// (fm_embedding_fwd_last_form names the one a launch set ran): tables of one bag size get the same
+// grid each (blockIdx.y = table) -- fm_emb_fwd_multi, whose single-lookup bags take emb_bal_short
+// ("multi_su"), fm_emb_fwd_split for long bags on small batches, fm_emb_fwd_multi_scalar for
+// D % 4 != 0; tables of unequal bag sizes (per-table multi-hot sizes) share a one-dimensional grid
+// dealt out by lookups -- "work-balanced forward" below.
 // Backward (fused sparse SGD: W[idx] -= lr*scale*dy; or dense-grad accumulate when lr == null):
+//   * mostly-unique tables with claim buffers: owner-computes (claim / dup / owner kernels), plain
+//     16-B read-modify-writes of the touched rows instead of row atomics;
 //   * regular tables: one wave-instruction = 64 consecutive fp32 atomic adds (256 contiguous bytes:
 //     the full gfx950 atomic rate, MI355X_MICROARCH "Global float atomics");
 //   * tiny tables (<= 64 rows: 3, 4, 10, 14, 36, 63 rows in the MLPerf set): thousands of samples hit the
@@ -25,6 +30,10 @@
 // dups) sums the duplicate lookups of a row, then fm_emb_adagrad_apply updates the accumulator and
 // the weights of the touched rows only -- see "fused sparse Adagrad" below; row-wise Adagrad keeps
 // one accumulator per row and also takes replicated tables -- "fused sparse row-wise Adagrad".
+// Said once and shared: the lane-group map (lane_map_vec / lane_map_scalar, host mirrors rpi_vec /
+// rpi_scalar), the four-wide output store (emb_store4), gradient load (emb_grad4) and gather-sum
+// (emb_gather_sum), and on the host the launch-set loop (for_each_batch / for_each_width_batch)
+// and the (element type, index width) dispatch (with_types).
 #include "common.h"
 
 #include <algorithm>
@@ -35,7 +44,6 @@
 namespace {
 
 constexpr int MAXT = 32;
-constexpr int TINY_ROWS = 16;
 
 // Row-sharded tables (SOAP row split of the embedding weight): a shard holds the global rows
 // [lo, lo + rows); lookups outside it contribute nothing here (their partial sums come from the
@@ -69,172 +77,29 @@ FM_DEVICE long ldi(const void* p, long i) {
   else return (long)reinterpret_cast<const int*>(p)[i];
 }
 
-template <typename OutT, bool I64>
-__global__ void __launch_bounds__(256) fm_emb_fwd_multi(TabSet s, long B, int su) {
-  const TabDesc& d = s.t[blockIdx.y];
-  const int D4 = d.D >> 2;
-  const int lpr = D4 < 64 ? D4 : 64;              // lanes per row (D <= 256)
-  const int rpi = 256 / lpr;                       // rows per block-iteration
-  const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
-  if (sub >= rpi) return;
-  const long bstride = (long)gridDim.x * rpi;
-  if (su && d.bag == 1 && D4 <= 64) {
-    // one lookup per sample (the MLPerf tables): SU samples' index loads, then their row loads in
-    // flight per lane, so a small grid still streams at the HBM rate and leaves CU slots to the
-    // bottom-MLP GEMMs running beside it on the other stream
-    constexpr int SU = 4;
-    const int c = lc * 4;
-    for (long b0 = (long)blockIdx.x * rpi + sub; b0 < B; b0 += SU * bstride) {
-      long r[SU];
-      bool ok[SU];
-#pragma unroll
-      for (int u = 0; u < SU; ++u) r[u] = local_row(ldi<I64>(d.idx, min(b0 + u * bstride, B - 1)), d.lo, d.rows, ok[u]);
-      f32x4_t v[SU];
-#pragma unroll
-      for (int u = 0; u < SU; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(d.W + r[u] * d.D + c);
-#pragma unroll
-      for (int u = 0; u < SU; ++u) {
-        const long b = b0 + u * bstride;
-        if (b >= B) break;
-        f32x4_t acc = ok[u] ? v[u] * d.scale : f32x4_t{0.f, 0.f, 0.f, 0.f};
-        OutT* o = reinterpret_cast<OutT*>(d.act) + b * d.ld + c;
-        if constexpr (sizeof(OutT) == 4) {
-          *reinterpret_cast<f32x4_t*>(o) = acc;
-        } else {
-          bf16x4_t w;
-          w[0] = (short)f2bf(acc[0]); w[1] = (short)f2bf(acc[1]); w[2] = (short)f2bf(acc[2]); w[3] = (short)f2bf(acc[3]);
-          *reinterpret_cast<bf16x4_t*>(o) = w;
-        }
-      }
-    }
-    return;
-  }
-  for (long b = (long)blockIdx.x * rpi + sub; b < B; b += bstride) {
-    for (int c4 = lc; c4 < D4; c4 += lpr) {
-      const int c = c4 * 4;
-      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-      int j = 0;
-      // long bags (summit_large: 100 lookups per sample, 256 samples): 8 index loads, then 8 row
-      // loads in flight per lane instead of one dependent index -> row round trip per lookup
-      for (; j + 8 <= d.bag; j += 8) {
-        long r[8];
-        bool ok[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) r[u] = local_row(ldi<I64>(d.idx, b * d.bag + j + u), d.lo, d.rows, ok[u]);
-        f32x4_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(d.W + r[u] * d.D + c);
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (ok[u]) acc += v[u];
-      }
-      for (; j < d.bag; ++j) {
-        bool ok;
-        const long r = local_row(ldi<I64>(d.idx, b * d.bag + j), d.lo, d.rows, ok);
-        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(d.W + r * d.D + c);
-        if (ok) acc += v;
-      }
-      acc *= d.scale;
-      OutT* o = reinterpret_cast<OutT*>(d.act) + b * d.ld + c;
-      if constexpr (sizeof(OutT) == 4) {
-        *reinterpret_cast<f32x4_t*>(o) = acc;
-      } else {
-        bf16x4_t v;
-        v[0] = (short)f2bf(acc[0]); v[1] = (short)f2bf(acc[1]); v[2] = (short)f2bf(acc[2]); v[3] = (short)f2bf(acc[3]);
-        *reinterpret_cast<bf16x4_t*>(o) = v;
-      }
-    }
-  }
-}
-
-// Long bags on small batches (summit_large: 256 samples x 100 lookups per table): one lane group
-// per sample leaves ~100 blocks for 256 CUs, each lane walking the whole bag.  Here SP lane groups
-// share a sample -- group k sums lookups k, k+SP, ... -- and the block folds the SP partial rows
-// through LDS.  D <= 256 (one 16-B column chunk per lane, lpr = D/4 lanes per row).
-template <typename OutT, bool I64>
-__global__ void __launch_bounds__(256) fm_emb_fwd_split(TabSet s, long B, int sp) {
-  __shared__ f32x4_t part[256];
-  const TabDesc& d = s.t[blockIdx.y];
-  const int lpr = d.D >> 2;                        // <= 64
-  const int rpi = 256 / lpr;                       // lane groups per block
-  const int spb = rpi / sp;                        // samples per block
-  const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
-  const bool live = sub < spb * sp;                // whole sample groups only
-  const int si = sub / sp, k = sub - si * sp;
-  const long b = (long)blockIdx.x * spb + si;
-  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-  if (live && b < B) {
-    const int c = lc * 4;
-    int j = k;
-    for (; j + 3 * sp < d.bag; j += 4 * sp) {
-      long r[4];
-      bool ok[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = local_row(ldi<I64>(d.idx, b * d.bag + j + u * sp), d.lo, d.rows, ok[u]);
-      f32x4_t v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(d.W + r[u] * d.D + c);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (ok[u]) acc += v[u];
-    }
-    for (; j < d.bag; j += sp) {
-      bool ok;
-      const long r = local_row(ldi<I64>(d.idx, b * d.bag + j), d.lo, d.rows, ok);
-      const f32x4_t v = *reinterpret_cast<const f32x4_t*>(d.W + r * d.D + c);
-      if (ok) acc += v;
-    }
-  }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  if (!live || k != 0 || b >= B) return;
-  for (int q = 1; q < sp; ++q) acc += part[threadIdx.x + q * lpr];
-  acc *= d.scale;
-  OutT* o = reinterpret_cast<OutT*>(d.act) + b * d.ld + lc * 4;
-  if constexpr (sizeof(OutT) == 4) {
-    *reinterpret_cast<f32x4_t*>(o) = acc;
-  } else {
-    bf16x4_t v;
-    v[0] = (short)f2bf(acc[0]); v[1] = (short)f2bf(acc[1]); v[2] = (short)f2bf(acc[2]); v[3] = (short)f2bf(acc[3]);
-    *reinterpret_cast<bf16x4_t*>(o) = v;
-  }
-}
-
-// scalar fallback for D % 4 != 0 (any D)
-template <typename OutT, bool I64>
-__global__ void __launch_bounds__(256) fm_emb_fwd_multi_scalar(TabSet s, long B) {
-  const TabDesc& d = s.t[blockIdx.y];
-  const int lpr = d.D < 256 ? d.D : 256;
-  const int rpi = 256 / lpr;
-  const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
-  if (sub >= rpi) return;
-  for (long b = (long)blockIdx.x * rpi + sub; b < B; b += (long)gridDim.x * rpi)
-    for (int c = lc; c < d.D; c += lpr) {
-      float acc = 0.f;
-      for (int j = 0; j < d.bag; ++j) {
-        bool ok;
-        const long r = local_row(ldi<I64>(d.idx, b * d.bag + j), d.lo, d.rows, ok);
-        const float v = d.W[r * d.D + c];
-        if (ok) acc += v;
-      }
-      st<OutT>(reinterpret_cast<OutT*>(d.act) + b * d.ld + c, acc * d.scale);
-    }
-}
-
-// ---- work-balanced forward for tables of UNEQUAL bag sizes (per-table multi-hot sizes) --------
-// fm_emb_fwd_multi gives every table the same grid; with the MLPerf multi-hot sizes (1..100
-// lookups per sample, 214 in all) the bag-100 table does 47 % of the row reads on 1/26 of the
-// blocks.  Here the grid is one dimension and the host deals the blocks out in proportion to each
-// table's lookups (first[i] = first block of table i); a block finds its table by a wave-uniform
-// scan of first[], then strides over that table's samples with its local id and that table's
-// block count.  lpr / rpi are per table, so tables of different D share a launch.  The sums run in
-// ascending bag order with the arithmetic and the stores of fm_emb_fwd_multi: the outputs are equal
-// bit for bit.  Every load is unconditional at a clamped address (see the header).
-struct BalSet {
-  TabDesc t[MAXT];
-  int first[MAXT + 1];
-  int n;
+// Lane-group map: the 256 threads of a block form rpi groups of lpr lanes, one group per row (a
+// sample, a lookup or a payload row).  sub = this thread's group, lc = its lane in the group; the
+// threads left over when lpr does not divide 256 are not live.
+struct LaneMap {
+  int lpr, rpi, sub, lc;
+  bool live;
 };
+FM_DEVICE LaneMap lane_map(int want, int cap) {
+  LaneMap m;
+  m.lpr = want < cap ? want : cap;
+  m.rpi = 256 / m.lpr;
+  m.sub = threadIdx.x / m.lpr;
+  m.lc = threadIdx.x - m.sub * m.lpr;
+  m.live = m.sub < m.rpi;
+  return m;
+}
+// vector form: a lane owns 4 consecutive columns (one 16-B access), at most 64 lanes per row
+FM_DEVICE LaneMap lane_map_vec(int D) { return lane_map(D >> 2, 64); }
+// scalar form: a lane owns a column, at most 256 lanes per row
+FM_DEVICE LaneMap lane_map_scalar(int D) { return lane_map(D, 256); }
+// the host's mirrors: rows per block-iteration of a table of D columns
+inline int rpi_vec(int D) { return 256 / std::min(64, std::max(1, D / 4)); }
+inline int rpi_scalar(int D) { return 256 / std::min(256, std::max(1, D)); }
 
 template <typename OutT>
 FM_DEVICE void emb_store4(OutT* o, const f32x4_t acc) {
@@ -245,6 +110,37 @@ FM_DEVICE void emb_store4(OutT* o, const f32x4_t acc) {
     w[0] = (short)f2bf(acc[0]); w[1] = (short)f2bf(acc[1]); w[2] = (short)f2bf(acc[2]); w[3] = (short)f2bf(acc[3]);
     *reinterpret_cast<bf16x4_t*>(o) = w;
   }
+}
+
+// four consecutive gradients (bf16: one 8-B load, fp32: one 16-B load) as fp32
+template <typename GT>
+FM_DEVICE f32x4_t emb_grad4(const GT* p) {
+  if constexpr (sizeof(GT) == 2) {
+    const bf16x4_t g = *reinterpret_cast<const bf16x4_t*>(p);
+    return f32x4_t{bf2f((unsigned short)g[0]), bf2f((unsigned short)g[1]), bf2f((unsigned short)g[2]),
+                   bf2f((unsigned short)g[3])};
+  } else {
+    return *reinterpret_cast<const f32x4_t*>(p);
+  }
+}
+
+// acc + the rows of lookup entries e0, e0 + stride, ..., e0 + (U - 1) * stride at columns [c, c + 4):
+// U index loads, then U row loads in flight per lane (instead of one dependent index -> row round
+// trip per lookup), then the adds in ascending order, each predicated on its shard holding the row.
+// acc goes in and out by value: by reference the eight-wide instance took 2 more VGPRs.
+template <bool I64, int U>
+FM_DEVICE f32x4_t emb_gather_sum(const TabDesc& d, long e0, int stride, int c, f32x4_t acc) {
+  long r[U];
+  bool ok[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) r[u] = local_row(ldi<I64>(d.idx, e0 + u * stride), d.lo, d.rows, ok[u]);
+  f32x4_t v[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) v[u] = *reinterpret_cast<const f32x4_t*>(d.W + r[u] * d.D + c);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (ok[u]) acc += v[u];
+  return acc;
 }
 
 // bags of at most U lookups: S samples' index loads, then their S * U row loads in flight per lane
@@ -278,6 +174,98 @@ FM_DEVICE void emb_bal_short(const TabDesc& d, long B, long b_first, long bstrid
   }
 }
 
+template <typename OutT, bool I64>
+__global__ void __launch_bounds__(256) fm_emb_fwd_multi(TabSet s, long B) {
+  const TabDesc& d = s.t[blockIdx.y];
+  const LaneMap m = lane_map_vec(d.D);
+  if (!m.live) return;
+  const int D4 = d.D >> 2;
+  const long bstride = (long)gridDim.x * m.rpi, b_first = (long)blockIdx.x * m.rpi + m.sub;
+  // the bag loop stands first and the single-lookup call last: the other way round the compiler
+  // spends 4 more VGPRs on the bag loop (profiles/embedding_refactor_device_diff.txt)
+  if (d.bag != 1 || D4 > 64) {
+    for (long b = b_first; b < B; b += bstride) {
+      for (int c4 = m.lc; c4 < D4; c4 += m.lpr) {
+        const int c = c4 * 4;
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+        int j = 0;
+        // long bags (summit_large: 100 lookups per sample, 256 samples): eight lookups at a time
+        for (; j + 8 <= d.bag; j += 8) acc = emb_gather_sum<I64, 8>(d, b * d.bag + j, 1, c, acc);
+        for (; j < d.bag; ++j) acc = emb_gather_sum<I64, 1>(d, b * d.bag + j, 0, c, acc);
+        acc *= d.scale;
+        emb_store4<OutT>(reinterpret_cast<OutT*>(d.act) + b * d.ld + c, acc);
+      }
+    }
+    return;
+  }
+  // one lookup per sample (the MLPerf tables): four samples' index loads, then their row loads in
+  // flight per lane, so a small grid still streams at the HBM rate and leaves CU slots to the
+  // bottom-MLP GEMMs running beside it on the other stream
+  emb_bal_short<OutT, I64, 4, 1>(d, B, b_first, bstride, m.lc * 4);
+}
+
+// Long bags on small batches (summit_large: 256 samples x 100 lookups per table): one lane group
+// per sample leaves ~100 blocks for 256 CUs, each lane walking the whole bag.  Here SP lane groups
+// share a sample -- group k sums lookups k, k+SP, ... -- and the block folds the SP partial rows
+// through LDS.  D <= 256 (one 16-B column chunk per lane, lpr = D/4 lanes per row).
+template <typename OutT, bool I64>
+__global__ void __launch_bounds__(256) fm_emb_fwd_split(TabSet s, long B, int sp) {
+  __shared__ f32x4_t part[256];
+  const TabDesc& d = s.t[blockIdx.y];
+  const LaneMap m = lane_map_vec(d.D);             // rpi lane groups per block
+  const int spb = m.rpi / sp;                      // samples per block
+  const bool live = m.sub < spb * sp;              // whole sample groups only
+  const int si = m.sub / sp, k = m.sub - si * sp;
+  const long b = (long)blockIdx.x * spb + si;
+  f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+  if (live && b < B) {
+    const int c = m.lc * 4;
+    int j = k;
+    for (; j + 3 * sp < d.bag; j += 4 * sp) acc = emb_gather_sum<I64, 4>(d, b * d.bag + j, sp, c, acc);
+    for (; j < d.bag; j += sp) acc = emb_gather_sum<I64, 1>(d, b * d.bag + j, 0, c, acc);
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  if (!live || k != 0 || b >= B) return;
+  for (int q = 1; q < sp; ++q) acc += part[threadIdx.x + q * m.lpr];
+  acc *= d.scale;
+  emb_store4<OutT>(reinterpret_cast<OutT*>(d.act) + b * d.ld + m.lc * 4, acc);
+}
+
+// scalar fallback for D % 4 != 0 (any D)
+template <typename OutT, bool I64>
+__global__ void __launch_bounds__(256) fm_emb_fwd_multi_scalar(TabSet s, long B) {
+  const TabDesc& d = s.t[blockIdx.y];
+  const LaneMap m = lane_map_scalar(d.D);
+  if (!m.live) return;
+  for (long b = (long)blockIdx.x * m.rpi + m.sub; b < B; b += (long)gridDim.x * m.rpi)
+    for (int c = m.lc; c < d.D; c += m.lpr) {
+      float acc = 0.f;
+      for (int j = 0; j < d.bag; ++j) {
+        bool ok;
+        const long r = local_row(ldi<I64>(d.idx, b * d.bag + j), d.lo, d.rows, ok);
+        const float v = d.W[r * d.D + c];
+        if (ok) acc += v;
+      }
+      st<OutT>(reinterpret_cast<OutT*>(d.act) + b * d.ld + c, acc * d.scale);
+    }
+}
+
+// ---- work-balanced forward for tables of UNEQUAL bag sizes (per-table multi-hot sizes) --------
+// fm_emb_fwd_multi gives every table the same grid; with the MLPerf multi-hot sizes (1..100
+// lookups per sample, 214 in all) the bag-100 table does 47 % of the row reads on 1/26 of the
+// blocks.  Here the grid is one dimension and the host deals the blocks out in proportion to each
+// table's lookups (first[i] = first block of table i); a block finds its table by a wave-uniform
+// scan of first[], then strides over that table's samples with its local id and that table's
+// block count.  lpr / rpi are per table, so tables of different D share a launch.  The sums run in
+// ascending bag order with the arithmetic and the stores of fm_emb_fwd_multi: the outputs are equal
+// bit for bit.  Every load is unconditional at a clamped address (see the header).
+struct BalSet {
+  TabDesc t[MAXT];
+  int first[MAXT + 1];
+  int n;
+};
+
 template <typename OutT, bool I64, int U>
 __global__ void __launch_bounds__(256) fm_emb_fwd_balanced(BalSet s, long B) {
   const int bid = blockIdx.x;
@@ -285,12 +273,10 @@ __global__ void __launch_bounds__(256) fm_emb_fwd_balanced(BalSet s, long B) {
   for (int i = 1; i < s.n; ++i) ti += bid >= s.first[i];      // first[] ascends: wave-uniform scan
   const TabDesc& d = s.t[ti];
   const int lb = bid - s.first[ti], nb = s.first[ti + 1] - s.first[ti];
-  const int lpr = d.D >> 2;                        // D <= 256: one 16-B column chunk per lane
-  const int rpi = 256 / lpr;
-  const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
-  if (sub >= rpi) return;
-  const int c = lc * 4;
-  const long bstride = (long)nb * rpi, b_first = (long)lb * rpi + sub;
+  const LaneMap m = lane_map_vec(d.D);             // D <= 256: one 16-B column chunk per lane
+  if (!m.live) return;
+  const int c = m.lc * 4;
+  const long bstride = (long)nb * m.rpi, b_first = (long)lb * m.rpi + m.sub;
   if (d.bag == 1) return emb_bal_short<OutT, I64, 4, 1>(d, B, b_first, bstride, c);
   if (d.bag <= 4) return emb_bal_short<OutT, I64, 2, 4>(d, B, b_first, bstride, c);
   // longer bags in chunks of U: the chunk's U row loads and the NEXT chunk's U index loads are in
@@ -325,16 +311,14 @@ template <typename GT, bool I64>
 __global__ void __launch_bounds__(256) fm_emb_bwd_atomic_multi(TabSet s, const float* __restrict__ lr, long B) {
   const TabDesc& d = s.t[blockIdx.y];
   const float mul = (lr ? -lr[0] : 1.f) * d.scale;
-  const int lpr = d.D < 256 ? d.D : 256;
-  const int rpi = 256 / lpr;
-  const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
-  if (sub >= rpi) return;
+  const LaneMap m = lane_map_scalar(d.D);
+  if (!m.live) return;
   float* W = const_cast<float*>(d.W);
   const GT* dy = reinterpret_cast<const GT*>(d.act);
-  for (long b = (long)blockIdx.x * rpi + sub; b < B; b += (long)gridDim.x * rpi) {
+  for (long b = (long)blockIdx.x * m.rpi + m.sub; b < B; b += (long)gridDim.x * m.rpi) {
     bool ok0;
     const long r0 = local_row(ldi<I64>(d.idx, b * d.bag), d.lo, d.rows, ok0);
-    for (int c = lc; c < d.D; c += lpr) {
+    for (int c = m.lc; c < d.D; c += m.lpr) {
       const float g = ld<GT>(dy + b * d.ld + c) * mul;
       if (ok0) atomicAdd(W + r0 * d.D + c, g);
       for (int j = 1; j < d.bag; ++j) {
@@ -398,6 +382,44 @@ __global__ void __launch_bounds__(256) fm_emb_bwd_tiny_multi(TabSet s, const flo
   }
 }
 
+// ---- host helpers -------------------------------------------------------------------------------
+// The tables k < n that take(k) accepts, cut into launch sets of at most MAXT: fn(ks, m) gets the
+// table numbers ks[0 .. m) of one set.
+template <typename Take, typename Fn>
+void for_each_batch(int n, Take take, Fn fn) {
+  std::vector<int> sel;
+  for (int k = 0; k < n; ++k)
+    if (take(k)) sel.push_back(k);
+  for (size_t base = 0; base < sel.size(); base += MAXT)
+    fn(sel.data() + base, (int)std::min<size_t>(MAXT, sel.size() - base));
+}
+// the same per index width (the width is a template parameter of the kernels, so a launch set holds
+// one width): int32 tables first, then int64; fn(ks, m, wide)
+template <typename Take, typename Fn>
+void for_each_width_batch(int n, const int* idx64, Take take, Fn fn) {
+  for (int w = 0; w < 2; ++w) {
+    const bool wide = w != 0;
+    for_each_batch(n, [&](int k) { return (idx64[k] != 0) == wide && take(k); },
+                   [&](const int* ks, int m) { fn(ks, m, wide); });
+  }
+}
+inline bool every_table(int) { return true; }
+
+// (bf16?, int64?) -> template arguments: fn gets a value whose type names the activation / gradient
+// element type (T::elem) and the index width (T::wide)
+template <typename E, bool W>
+struct EmbTypes {
+  using elem = E;
+  static constexpr bool wide = W;
+};
+template <typename Fn>
+void with_types(bool bf16, bool wide, Fn fn) {
+  if (bf16 && wide) fn(EmbTypes<unsigned short, true>{});
+  else if (bf16) fn(EmbTypes<unsigned short, false>{});
+  else if (wide) fn(EmbTypes<float, true>{});
+  else fn(EmbTypes<float, false>{});
+}
+
 // fm_embedding_set_fwd_mode: 0 = auto (balanced for vectorisable sets of unequal bags), 1 = never
 // balanced, 2 = balanced for every vectorisable set.  Auto takes the balanced kernel because it
 // measured 226 -> 171 us (fp32 out) and 200 -> 154 us (bf16 out) on the 26 MLPerf multi-hot tables at
@@ -414,15 +436,15 @@ thread_local int g_emb_fwd_form = FWD_NONE;
 // Block shares: the budget is the grid fm_emb_fwd_multi would launch (so the forward takes the same
 // share of the chip beside the bottom-MLP GEMMs); table i gets blocks in proportion to its lookups
 // B * bag_i, at least one and at most one per rows-per-iteration of its samples.
-template <bool I64>
-void launch_balanced(const TabSet& s, int m, bool out_bf16, long B, long budget, hipStream_t st) {
+template <typename OutT, bool I64>
+void launch_balanced(const TabSet& s, int m, long B, long budget, hipStream_t st) {
   BalSet bs;
   long sumbag = 0;
   for (int i = 0; i < m; ++i) sumbag += s.t[i].bag;
   bs.first[0] = 0;
   for (int i = 0; i < m; ++i) {
     bs.t[i] = s.t[i];
-    const int rpi = 256 / (s.t[i].D / 4);
+    const int rpi = rpi_vec(s.t[i].D);
     const long cap = (B + rpi - 1) / rpi;
     const long want = (budget * s.t[i].bag + sumbag / 2) / sumbag;
     bs.first[i + 1] = bs.first[i] + (int)std::max<long>(1, std::min(want, cap));
@@ -430,18 +452,17 @@ void launch_balanced(const TabSet& s, int m, bool out_bf16, long B, long budget,
   for (int i = m + 1; i <= MAXT; ++i) bs.first[i] = bs.first[m];
   bs.n = m;
   const dim3 grid((unsigned)bs.first[m]);
-  if (out_bf16) hipLaunchKernelGGL((fm_emb_fwd_balanced<unsigned short, I64, BAL_U>), grid, dim3(256), 0, st, bs, B);
-  else hipLaunchKernelGGL((fm_emb_fwd_balanced<float, I64, BAL_U>), grid, dim3(256), 0, st, bs, B);
+  hipLaunchKernelGGL((fm_emb_fwd_balanced<OutT, I64, BAL_U>), grid, dim3(256), 0, st, bs, B);
 }
 
-template <bool I64>
-void launch_fwd(const TabSet& s, int m, bool vec, bool out_bf16, long B, int D0, hipStream_t st) {
-  const int rpi = std::max(1, 256 / std::min(64, std::max(1, D0 / 4)));
+template <typename OutT, bool I64>
+void launch_fwd(const TabSet& s, int m, bool vec, long B, int D0, hipStream_t st) {
+  const int rpi = rpi_vec(D0);
   bool uniform = true;
   for (int i = 1; i < m; ++i) uniform = uniform && s.t[i].bag == s.t[0].bag;
   if (vec && (g_emb_fwd_mode == 2 || (g_emb_fwd_mode == 0 && !uniform))) {
     const long budget = std::max<long>(1, std::min<long>((B + rpi - 1) / rpi, 256L)) * m;
-    launch_balanced<I64>(s, m, out_bf16, B, budget, st);
+    launch_balanced<OutT, I64>(s, m, B, budget, st);
     g_emb_fwd_form = FWD_BALANCED;
     return;
   }
@@ -459,8 +480,7 @@ void launch_fwd(const TabSet& s, int m, bool vec, bool out_bf16, long B, int D0,
     if (sp > 1) {
       const int spb = rpi / sp;
       dim3 grid((unsigned)((B + spb - 1) / spb), m);
-      if (out_bf16) hipLaunchKernelGGL((fm_emb_fwd_split<unsigned short, I64>), grid, dim3(256), 0, st, s, B, sp);
-      else hipLaunchKernelGGL((fm_emb_fwd_split<float, I64>), grid, dim3(256), 0, st, s, B, sp);
+      hipLaunchKernelGGL((fm_emb_fwd_split<OutT, I64>), grid, dim3(256), 0, st, s, B, sp);
       g_emb_fwd_form = FWD_SPLIT;
       return;
     }
@@ -468,17 +488,15 @@ void launch_fwd(const TabSet& s, int m, bool vec, bool out_bf16, long B, int D0,
   // 256 blocks per table: the forward runs beside the bottom MLP on a second stream; fewer,
   // longer-running blocks leave CUs to its GEMMs: MLPerf fp32 step 1.181 ms at 2048 blocks per
   // table, 1.164 at 256, 1.172 at 64 (profiles/bench_ab_x3_sched_embgrid_r5n.txt).  Single-lookup
-  // bags take two samples per lane-group iteration (su; profiles/bench_ab_emb_fwd_su_r5zc.txt)
+  // bags take four samples per lane-group iteration (emb_bal_short<.., 4, 1>;
+  // profiles/bench_ab_emb_fwd_su_r5zc.txt)
   dim3 grid((unsigned)std::max<long>(1, std::min<long>((B + rpi - 1) / rpi, 256L)), m);
-  const int su = 1;
   if (vec) {
-    if (out_bf16) hipLaunchKernelGGL((fm_emb_fwd_multi<unsigned short, I64>), grid, dim3(256), 0, st, s, B, su);
-    else hipLaunchKernelGGL((fm_emb_fwd_multi<float, I64>), grid, dim3(256), 0, st, s, B, su);
+    hipLaunchKernelGGL((fm_emb_fwd_multi<OutT, I64>), grid, dim3(256), 0, st, s, B);
     g_emb_fwd_form = uniform && s.t[0].bag == 1 ? FWD_MULTI_SU : FWD_MULTI;   // su: the single-lookup loop
   } else {
     g_emb_fwd_form = FWD_SCALAR;
-    if (out_bf16) hipLaunchKernelGGL((fm_emb_fwd_multi_scalar<unsigned short, I64>), grid, dim3(256), 0, st, s, B);
-    else hipLaunchKernelGGL((fm_emb_fwd_multi_scalar<float, I64>), grid, dim3(256), 0, st, s, B);
+    hipLaunchKernelGGL((fm_emb_fwd_multi_scalar<OutT, I64>), grid, dim3(256), 0, st, s, B);
   }
 }
 
@@ -536,143 +554,53 @@ template <typename GT, bool I64>
 __global__ void __launch_bounds__(256) fm_emb_owner_multi(ClaimSet s, const float* __restrict__ lr, long B) {
   const ClaimDesc& d = s.t[blockIdx.y];
   const float mul = -lr[0] * d.scale;
+  const LaneMap m = lane_map_vec(d.D);
   const int D4 = d.D >> 2;
-  const int lpr = D4 < 64 ? D4 : 64;
-  const int rpi = 256 / lpr;
-  const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
   const long n = B * d.bag;
   const GT* dy = reinterpret_cast<const GT*>(d.dy);
-  if (sub < rpi) {
-    for (long e = (long)blockIdx.x * rpi + sub; e < n; e += (long)gridDim.x * rpi) {
+  if (m.live) {
+    for (long e = (long)blockIdx.x * m.rpi + m.sub; e < n; e += (long)gridDim.x * m.rpi) {
       bool ok;
       const long r = local_row(ldi<I64>(d.idx, e), d.lo, d.rows, ok);
       if (!ok || d.owner[r] != (int)e) continue;   // uniform across the row's lanes
       const long b = e / d.bag;
-      for (int c4 = lc; c4 < D4; c4 += lpr) {
+      for (int c4 = m.lc; c4 < D4; c4 += m.lpr) {
         const int c = c4 * 4;
         f32x4_t* wp = reinterpret_cast<f32x4_t*>(d.W + r * d.D + c);
         f32x4_t w = *wp;
-        if constexpr (sizeof(GT) == 2) {
-          const bf16x4_t g = *reinterpret_cast<const bf16x4_t*>(dy + b * d.ld + c);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) w[j] += mul * bf2f((unsigned short)g[j]);
-        } else {
-          const f32x4_t g = *reinterpret_cast<const f32x4_t*>(dy + b * d.ld + c);
-          w += mul * g;
-        }
+        w += mul * emb_grad4<GT>(dy + b * d.ld + c);
         *wp = w;
       }
-      if (lc == 0) d.owner[r] = -1;                // release the claim for the next step
+      if (m.lc == 0) d.owner[r] = -1;                // release the claim for the next step
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) *d.ndup = 0;   // the dup kernel has finished reading it
 }
 
-// ---- count-based sparse SGD (fm_embedding_set_bwd_mode(1)): two launches for every non-tiny table ---
-// count: every in-shard lookup e adds one to its row's slot (slot = lookups - 1; -1 = untouched)
-// and records in own[e] (the dups array) whether it arrived first.  update: a lookup whose row was
-// hit exactly once (slot == 0) applies a plain 16-B read-modify-write and frees the slot; rows hit
-// more often take float atomics (lane = column: 256 contiguous bytes per wave-instruction) and
-// their first arrival frees the slot.  A freed slot reads -1, never 0, so the plain path stays
-// exclusive to single-lookup rows whatever the order of the lookups -- the claim / dup / owner
-// kernels' work in one pass, and the mid-size tables (where most rows repeat) no longer need a
-// kernel of their own.
-template <bool I64>
-__global__ void __launch_bounds__(256) fm_emb_count_multi(ClaimSet s, long B) {
-  const ClaimDesc& d = s.t[blockIdx.y];
-  const long n = B * d.bag;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-    bool ok;
-    const long r = local_row(ldi<I64>(d.idx, e), d.lo, d.rows, ok);
-    int own = 0;
-    if (ok) own = atomicAdd(d.owner + r, 1) == -1;
-    d.dups[e] = own;
-  }
+// the grid-stride backward kernels (claim / dup / owner / atomic) take their full grids, up to the
+// caps below
+template <typename GT, bool I64>
+void launch_claim(const ClaimSet& s, int m, const float* lr, long B, int maxbag, int minD, hipStream_t st) {
+  const long n = B * maxbag;
+  dim3 gc((unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 1024)), m);
+  hipLaunchKernelGGL((fm_emb_claim_multi<I64>), gc, dim3(256), 0, st, s, B);
+  // (a 64-block grid measured 18.4 vs 9.5 us/step: 12k..40k-row tables still see thousands of dups)
+  dim3 gd((unsigned)std::max<long>(1, std::min<long>((n + 3) / 4, 1024)), m);
+  hipLaunchKernelGGL((fm_emb_dup_multi<GT, I64>), gd, dim3(256), 0, st, s, lr);
+  const int rpi = rpi_vec(minD);
+  dim3 go((unsigned)std::max<long>(1, std::min<long>((n + rpi - 1) / rpi, 2048)), m);
+  hipLaunchKernelGGL((fm_emb_owner_multi<GT, I64>), go, dim3(256), 0, st, s, lr, B);
 }
 
 template <typename GT, bool I64>
-__global__ void __launch_bounds__(256) fm_emb_update_multi(ClaimSet s, const float* __restrict__ lr, long B) {
-  const ClaimDesc& d = s.t[blockIdx.y];
-  const float mul = -lr[0] * d.scale;
-  const int D4 = d.D >> 2;
-  const int lpr = D4 < 64 ? D4 : 64;
-  const int rpi = 256 / lpr;
-  const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
-  const long n = B * d.bag;
-  const GT* dy = reinterpret_cast<const GT*>(d.dy);
-  if (sub >= rpi) return;
-  for (long e = (long)blockIdx.x * rpi + sub; e < n; e += (long)gridDim.x * rpi) {
-    bool ok;
-    const long r = local_row(ldi<I64>(d.idx, e), d.lo, d.rows, ok);
-    if (!ok) continue;                                // uniform across the row's lanes
-    const int c = __hip_atomic_load(d.owner + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int own = d.dups[e];
-    const long b = e / d.bag;
-    const GT* g = dy + b * d.ld;
-    float* wr = d.W + r * d.D;
-    if (c == 0) {                                     // the row's only lookup: plain 16-B RMW
-      for (int c4 = lc; c4 < D4; c4 += lpr) {
-        const int col = c4 * 4;
-        f32x4_t* wp = reinterpret_cast<f32x4_t*>(wr + col);
-        f32x4_t w = *wp;
-        if constexpr (sizeof(GT) == 2) {
-          const bf16x4_t gv = *reinterpret_cast<const bf16x4_t*>(g + col);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) w[j] += mul * bf2f((unsigned short)gv[j]);
-        } else {
-          w += mul * *reinterpret_cast<const f32x4_t*>(g + col);
-        }
-        *wp = w;
-      }
-    } else {                                          // repeated row: lane = column atomics
-      for (int col = lc; col < d.D; col += lpr) atomicAdd(wr + col, mul * ld<GT>(g + col));
-    }
-    if (lc == 0 && (c == 0 || own)) __hip_atomic_store(d.owner + r, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-template <bool I64>
-void launch_count(const ClaimSet& s, int m, bool dy_bf16, const float* lr, long B, int maxbag, int minD4,
-                  hipStream_t st) {
-  const long n = B * maxbag;
-  dim3 gc((unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 1024)), m);
-  hipLaunchKernelGGL((fm_emb_count_multi<I64>), gc, dim3(256), 0, st, s, B);
-  const int rpi = 256 / std::min(64, std::max(1, minD4));
-  dim3 gu((unsigned)std::max<long>(1, std::min<long>((n + rpi - 1) / rpi, 2048)), m);
-  if (dy_bf16) hipLaunchKernelGGL((fm_emb_update_multi<unsigned short, I64>), gu, dim3(256), 0, st, s, lr, B);
-  else hipLaunchKernelGGL((fm_emb_update_multi<float, I64>), gu, dim3(256), 0, st, s, lr, B);
-}
-
-// blocks per table of the grid-stride backward kernels (claim / dup / owner / atomic): uncapped
-long emb_bwd_cap(long want) { return want; }
-
-template <bool I64>
-void launch_claim(const ClaimSet& s, int m, bool dy_bf16, const float* lr, long B, int maxbag, int minD4,
-                  hipStream_t st) {
-  const long n = B * maxbag;
-  dim3 gc((unsigned)std::max<long>(1, emb_bwd_cap(std::min<long>((n + 255) / 256, 1024))), m);
-  hipLaunchKernelGGL((fm_emb_claim_multi<I64>), gc, dim3(256), 0, st, s, B);
-  // (a 64-block grid measured 18.4 vs 9.5 us/step: 12k..40k-row tables still see thousands of dups)
-  dim3 gd((unsigned)std::max<long>(1, emb_bwd_cap(std::min<long>((n + 3) / 4, 1024))), m);
-  if (dy_bf16) hipLaunchKernelGGL((fm_emb_dup_multi<unsigned short, I64>), gd, dim3(256), 0, st, s, lr);
-  else hipLaunchKernelGGL((fm_emb_dup_multi<float, I64>), gd, dim3(256), 0, st, s, lr);
-  const int rpi = 256 / std::min(64, std::max(1, minD4));
-  dim3 go((unsigned)std::max<long>(1, emb_bwd_cap(std::min<long>((n + rpi - 1) / rpi, 2048))), m);
-  if (dy_bf16) hipLaunchKernelGGL((fm_emb_owner_multi<unsigned short, I64>), go, dim3(256), 0, st, s, lr, B);
-  else hipLaunchKernelGGL((fm_emb_owner_multi<float, I64>), go, dim3(256), 0, st, s, lr, B);
-}
-
-template <bool I64>
-void launch_bwd(const TabSet& s, int m, bool tiny, bool dy_bf16, const float* lr, long B, int maxD, hipStream_t st) {
+void launch_bwd(const TabSet& s, int m, bool tiny, const float* lr, long B, int maxD, hipStream_t st) {
   if (tiny) {
     size_t lds = 0;
     for (int i = 0; i < m; ++i) lds = std::max(lds, (size_t)s.t[i].rows * s.t[i].D * 4 * 4);  // one copy per wave
     static bool attr = false;
     if (!attr) {   // > 64 KiB of dynamic LDS (above 32 rows at D = 128) needs the opt-in
-      (void)hipFuncSetAttribute((const void*)fm_emb_bwd_tiny_multi<unsigned short, I64>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-      (void)hipFuncSetAttribute((const void*)fm_emb_bwd_tiny_multi<float, I64>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+      (void)hipFuncSetAttribute((const void*)fm_emb_bwd_tiny_multi<GT, I64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 << 10);
       attr = true;
     }
     // 64-sample chunks keep the per-wave chain to one round trip; at large B more blocks would
@@ -680,13 +608,11 @@ void launch_bwd(const TabSet& s, int m, bool tiny, bool dy_bf16, const float* lr
     // B=65536 -> 128..256)
     const int chunk = B <= 16384 ? 64 : B <= 32768 ? 128 : 256;
     dim3 grid((unsigned)((B + chunk - 1) / chunk), m);
-    if (dy_bf16) hipLaunchKernelGGL((fm_emb_bwd_tiny_multi<unsigned short, I64>), grid, dim3(256), lds, st, s, lr, B, chunk);
-    else hipLaunchKernelGGL((fm_emb_bwd_tiny_multi<float, I64>), grid, dim3(256), lds, st, s, lr, B, chunk);
+    hipLaunchKernelGGL((fm_emb_bwd_tiny_multi<GT, I64>), grid, dim3(256), lds, st, s, lr, B, chunk);
   } else {
-    const int rpi = std::max(1, 256 / std::min(256, maxD));
-    dim3 grid((unsigned)std::max<long>(1, emb_bwd_cap(std::min<long>((B + rpi - 1) / rpi, 2048))), m);
-    if (dy_bf16) hipLaunchKernelGGL((fm_emb_bwd_atomic_multi<unsigned short, I64>), grid, dim3(256), 0, st, s, lr, B);
-    else hipLaunchKernelGGL((fm_emb_bwd_atomic_multi<float, I64>), grid, dim3(256), 0, st, s, lr, B);
+    const int rpi = rpi_scalar(maxD);
+    dim3 grid((unsigned)std::max<long>(1, std::min<long>((B + rpi - 1) / rpi, 2048)), m);
+    hipLaunchKernelGGL((fm_emb_bwd_atomic_multi<GT, I64>), grid, dim3(256), 0, st, s, lr, B);
   }
 }
 
@@ -844,17 +770,15 @@ __global__ void __launch_bounds__(256) fm_emb_adagrad_apply_multi(AdaSet s, cons
   if (cnt <= 0) return;
   const float lr = lr_p[0];
   if (d.vec) {
-    const int D4 = d.D >> 2;
-    const int lpr = D4 < 64 ? D4 : 64;
-    const int rpi = 256 / lpr;
-    const int sub = threadIdx.x / lpr, lc = threadIdx.x - sub * lpr;
-    if (sub >= rpi) return;
-    const long stride = (long)gridDim.x * rpi;
-    for (long u0 = (long)blockIdx.x * rpi + sub; u0 < cnt; u0 += 2 * stride) {
+    const LaneMap m = lane_map_vec(d.D);
+    if (!m.live) return;
+    const int D4 = d.D >> 2, lc = m.lc;
+    const long stride = (long)gridDim.x * m.rpi;
+    for (long u0 = (long)blockIdx.x * m.rpi + m.sub; u0 < cnt; u0 += 2 * stride) {
       const bool live1 = u0 + stride < cnt;            // uniform across the row's lanes
       const long u1 = live1 ? u0 + stride : cnt - 1;
       const long r0 = d.ids[u0], r1 = d.ids[u1];
-      for (int c4 = lc; c4 < D4; c4 += lpr) {
+      for (int c4 = lc; c4 < D4; c4 += m.lpr) {
         const int c = c4 * 4;
         f32x4_t* hp0 = reinterpret_cast<f32x4_t*>(d.H + r0 * d.D + c);
         f32x4_t* wp0 = reinterpret_cast<f32x4_t*>(d.W + r0 * d.D + c);
@@ -1067,30 +991,25 @@ __global__ void __launch_bounds__(256) fm_sdp_rowwise_merge(RwMergeSet s) {
 
 // ------------------------------------------------------------------------------------------
 // Launchers.  Arrays describe n tables; act/ld = outputs (fwd) or output grads (bwd).  Tables
-// are batched by index width (and, in backward, by kernel kind) into launches of <= 32 tables.
+// are batched by index width (and, in backward, by kernel: owner-computes, tiny, atomic) into launches of <= 32 tables.
 // lo: first global row of each table shard (nullptr = whole tables); rows: rows held
 extern "C" void fm_embedding_fwd_multi(int n, const float* const* W, const void* const* idx, const int* idx64,
                                        void* const* out, const long* ldo, const long* lo, const int* rows, const int* D,
                                        const int* bag, const float* scale, int out_bf16, long B, hipStream_t st) {
   if (B <= 0) return;
-  for (int wide = 0; wide < 2; ++wide) {
-    std::vector<int> sel;
-    for (int k = 0; k < n; ++k)
-      if ((idx64[k] != 0) == (wide != 0)) sel.push_back(k);
-    for (size_t base = 0; base < sel.size(); base += MAXT) {
-      TabSet s;
-      int m = (int)std::min<size_t>(MAXT, sel.size() - base);
-      bool vec = true;
-      for (int i = 0; i < m; ++i) {
-        int k = sel[base + i];
-        s.t[i] = TabDesc{W[k], idx[k], out[k], ldo[k], lo ? lo[k] : 0, rows[k], D[k], bag[k], scale[k]};
-        vec = vec && (D[k] % 4 == 0) && (ldo[k] % 4 == 0) && D[k] <= 256;
-      }
-      s.n = m;
-      if (wide) launch_fwd<true>(s, m, vec, out_bf16, B, D[sel[base]], st);
-      else launch_fwd<false>(s, m, vec, out_bf16, B, D[sel[base]], st);
+  for_each_width_batch(n, idx64, every_table, [&](const int* ks, int m, bool wide) {
+    TabSet s;
+    bool vec = true;
+    for (int i = 0; i < m; ++i) {
+      const int k = ks[i];
+      s.t[i] = TabDesc{W[k], idx[k], out[k], ldo[k], lo ? lo[k] : 0, rows[k], D[k], bag[k], scale[k]};
+      vec = vec && (D[k] % 4 == 0) && (ldo[k] % 4 == 0) && D[k] <= 256;
     }
-  }
+    s.n = m;
+    with_types(out_bf16 != 0, wide, [&](auto t) {
+      launch_fwd<typename decltype(t)::elem, decltype(t)::wide>(s, m, vec, B, D[ks[0]], st);
+    });
+  });
 }
 
 extern "C" void fm_embedding_set_fwd_mode(int mode) { g_emb_fwd_mode = mode == 1 || mode == 2 ? mode : 0; }
@@ -1098,87 +1017,60 @@ extern "C" void fm_embedding_set_fwd_mode(int mode) { g_emb_fwd_mode = mode == 1
 // 4 scalar, 5 balanced
 extern "C" void fm_embedding_fwd_last_form(int* out) { out[0] = g_emb_fwd_form; }
 
-static int g_emb_count = 0;    // fm_embedding_set_bwd_mode: 1 = the count / update pair
-extern "C" void fm_embedding_set_bwd_mode(int count) { g_emb_count = count ? 1 : 0; }
-
 // lr != nullptr: fused sparse SGD into W; lr == nullptr: W is a dense grad buffer (accumulate).
 extern "C" void fm_embedding_bwd_multi(int n, float* const* W, const void* const* idx, const int* idx64,
                                        const void* const* dy, const long* ldg, const long* lo, const int* rows, const int* D,
                                        const int* bag, const float* scale, int dy_bf16, const float* lr, long B,
                                        int* const* owner, int* const* dups, int* const* ndup, hipStream_t st) {
   if (B <= 0) return;
-  // owner-computes path: fused SGD, claim buffers given, 16-B rows; count mode: the count / update
-  // pair instead of claim / dup / owner (the buffers are the same)
-  const bool count_mode = g_emb_count == 1;
+  // owner-computes path: fused SGD, claim buffers given, 16-B rows
   auto claimable = [&](int k) {
     return lr != nullptr && owner != nullptr && owner[k] != nullptr && D[k] % 4 == 0 && ldg[k] % 4 == 0 &&
            D[k] <= 256;
   };
-  for (int wide = 0; wide < 2; ++wide) {
-    std::vector<int> sel;
-    for (int k = 0; k < n; ++k)
-      if (claimable(k) && (idx64[k] != 0) == (wide != 0)) sel.push_back(k);
-    for (size_t base = 0; base < sel.size(); base += MAXT) {
-      ClaimSet s;
-      int m = (int)std::min<size_t>(MAXT, sel.size() - base);
-      int maxbag = 1, minD4 = 64;
-      for (int i = 0; i < m; ++i) {
-        int k = sel[base + i];
-        s.t[i] = ClaimDesc{W[k], idx[k], dy[k], ldg[k], lo ? lo[k] : 0, rows[k], D[k], bag[k], scale[k], owner[k], dups[k],
-                           ndup[k]};
-        maxbag = std::max(maxbag, bag[k]);
-        minD4 = std::min(minD4, D[k] / 4);
-      }
-      s.n = m;
-      if (count_mode) {
-        if (wide) launch_count<true>(s, m, dy_bf16, lr, B, maxbag, minD4, st);
-        else launch_count<false>(s, m, dy_bf16, lr, B, maxbag, minD4, st);
-      } else if (wide) {
-        launch_claim<true>(s, m, dy_bf16, lr, B, maxbag, minD4, st);
-      } else {
-        launch_claim<false>(s, m, dy_bf16, lr, B, maxbag, minD4, st);
-      }
+  for_each_width_batch(n, idx64, claimable, [&](const int* ks, int m, bool wide) {
+    ClaimSet s;
+    int maxbag = 1, minD = 256;
+    for (int i = 0; i < m; ++i) {
+      const int k = ks[i];
+      s.t[i] = ClaimDesc{W[k], idx[k], dy[k], ldg[k], lo ? lo[k] : 0, rows[k], D[k], bag[k], scale[k], owner[k], dups[k],
+                         ndup[k]};
+      maxbag = std::max(maxbag, bag[k]);
+      minD = std::min(minD, D[k]);
     }
-  }
-  // kind: 0 tiny (wave-private LDS copies), 2 regular (atomics).  Measured and deleted in r6: a
-  // block-shared LDS copy for 36..155-row tables (113 vs 16.6 us of regular atomics) and row-block
-  // ownership for <= 8192-row tables (76 vs 48 us; profiles/emb_bwd_rowblock_r5u.jsonl)
-  auto kind_of = [&](int k) {
-    // the wave-private LDS kernel up to TINY_ROWS rows while its four copies fit the LDS (rows * D *
+    s.n = m;
+    with_types(dy_bf16 != 0, wide, [&](auto t) {
+      launch_claim<typename decltype(t)::elem, decltype(t)::wide>(s, m, lr, B, maxbag, minD, st);
+    });
+  });
+  // the other tables: tiny (wave-private LDS copies) or regular (atomics).  Measured and deleted in
+  // r6: a block-shared LDS copy for 36..155-row tables (113 vs 16.6 us of regular atomics) and
+  // row-block ownership for <= 8192-row tables (76 vs 48 us; profiles/emb_bwd_rowblock_r5u.jsonl)
+  auto tiny = [&](int k) {
+    // the wave-private LDS kernel up to tiny_rows rows while its four copies fit the LDS (rows * D *
     // 16 B).  64 takes the 36- and 63-row MLPerf tables off the same-address atomics: slower alone
     // (35.5 vs 32.3 us for the eight <= 155-row tables) but less contention beside the bottom-MLP
     // backward, step 1.145-1.164 vs 1.170-1.173 ms at 16 (profiles/emb_tiny_rows_ab_r5tr.txt).  A
     // block-shared copy with LDS float atomics for <= 160 rows measured 93.5 vs 30.5 us (r7, removed).
     constexpr int tiny_rows = 64;
-    if (rows[k] <= tiny_rows && (long)rows[k] * D[k] * 16 <= (160L << 10) && D[k] <= 256 &&
-        B * (long)bag[k] >= 16L * rows[k])
-      return 0;
-    return 2;
+    return rows[k] <= tiny_rows && (long)rows[k] * D[k] * 16 <= (160L << 10) && D[k] <= 256 &&
+           B * (long)bag[k] >= 16L * rows[k];
   };
-  for (int pass = 0; pass < 4; ++pass) {
-    const int kind = (pass >> 1) * 2;
-    const bool tiny = kind == 0, wide = pass & 1;
-    std::vector<int> sel;
-    for (int k = 0; k < n; ++k) {
-      if (claimable(k)) continue;
-      if (kind_of(k) == kind && (idx64[k] != 0) == wide) sel.push_back(k);
-    }
-    for (size_t base = 0; base < sel.size(); base += MAXT) {
+  for (const bool want_tiny : {true, false}) {
+    for_each_width_batch(n, idx64, [&](int k) { return !claimable(k) && tiny(k) == want_tiny; },
+                         [&](const int* ks, int m, bool wide) {
       TabSet s;
-      int m = (int)std::min<size_t>(MAXT, sel.size() - base);
       int maxD = 1;
       for (int i = 0; i < m; ++i) {
-        int k = sel[base + i];
+        const int k = ks[i];
         s.t[i] = TabDesc{W[k], idx[k], const_cast<void*>(dy[k]), ldg[k], lo ? lo[k] : 0, rows[k], D[k], bag[k], scale[k]};
         maxD = std::max(maxD, D[k]);
       }
       s.n = m;
-      if (wide) {
-        launch_bwd<true>(s, m, tiny, dy_bf16, lr, B, maxD, st);
-      } else {
-        launch_bwd<false>(s, m, tiny, dy_bf16, lr, B, maxD, st);
-      }
-    }
+      with_types(dy_bf16 != 0, wide, [&](auto t) {
+        launch_bwd<typename decltype(t)::elem, decltype(t)::wide>(s, m, want_tiny, lr, B, maxD, st);
+      });
+    });
   }
 }
 
@@ -1207,31 +1099,24 @@ extern "C" void fm_sdp_coalesce(int n, const void* const* idx, const int* idx64,
                                 const long* lo, const int* rows, const int* D, const int* bag, const float* scale,
                                 int dy_bf16, long B, int* const* slot, int* const* cid, int* const* ids, float* const* g,
                                 int* const* count, hipStream_t st) {
-  if (B <= 0 || n <= 0) return;
-  static constexpr decltype(&launch_coalesce<float, false>) launch[2][2] = {      // [dy bf16][idx int64]
-      {launch_coalesce<float, false>, launch_coalesce<float, true>},
-      {launch_coalesce<unsigned short, false>, launch_coalesce<unsigned short, true>}};
-  for (int wide = 0; wide < 2; ++wide) {
-    std::vector<int> sel;
-    for (int k = 0; k < n; ++k)
-      if ((idx64[k] != 0) == (wide != 0)) sel.push_back(k);
-    for (size_t base = 0; base < sel.size(); base += MAXT) {
-      SdpSet s;
-      const int m = (int)std::min<size_t>(MAXT, sel.size() - base);
-      int maxbag = 1;
-      for (int i = 0; i < m; ++i) {
-        const int k = sel[base + i];
-        s.t[i] = SdpDesc{idx[k], dy[k], ldg[k], lo ? lo[k] : 0, rows[k], D[k], bag[k], scale[k], slot[k], cid[k], ids[k],
-                         g[k], count[k]};
-        maxbag = std::max(maxbag, bag[k]);
-      }
-      s.n = m;
-      const long ne = B * maxbag;
-      dim3 gc((unsigned)std::max<long>(1, std::min<long>((ne + 255) / 256, 1024)), m);
-      dim3 gw((unsigned)std::max<long>(1, std::min<long>((ne + 3) / 4, 2048)), m);
-      launch[dy_bf16 != 0][wide](s, gc, gw, B, st);
+  if (B <= 0) return;
+  for_each_width_batch(n, idx64, every_table, [&](const int* ks, int m, bool wide) {
+    SdpSet s;
+    int maxbag = 1;
+    for (int i = 0; i < m; ++i) {
+      const int k = ks[i];
+      s.t[i] = SdpDesc{idx[k], dy[k], ldg[k], lo ? lo[k] : 0, rows[k], D[k], bag[k], scale[k], slot[k], cid[k], ids[k],
+                       g[k], count[k]};
+      maxbag = std::max(maxbag, bag[k]);
     }
-  }
+    s.n = m;
+    const long ne = B * maxbag;
+    dim3 gc((unsigned)std::max<long>(1, std::min<long>((ne + 255) / 256, 1024)), m);
+    dim3 gw((unsigned)std::max<long>(1, std::min<long>((ne + 3) / 4, 2048)), m);
+    with_types(dy_bf16 != 0, wide, [&](auto t) {
+      launch_coalesce<typename decltype(t)::elem, decltype(t)::wide>(s, gc, gw, B, st);
+    });
+  });
 }
 
 // apply the gathered segments in order: segs x n tables; seg_ids/seg_g/seg_count[s*n + k]; the
@@ -1239,17 +1124,15 @@ extern "C" void fm_sdp_coalesce(int n, const void* const* idx, const int* idx64,
 extern "C" void fm_sdp_apply_segments(int n, int segs, int own_seg, float* const* W, const int* D, const int* const* seg_ids,
                                       const float* const* seg_g, const int* const* seg_count, int* const* slot,
                                       int* const* own_count, const int* nmax, const float* lr, hipStream_t st) {
-  if (n <= 0) return;
-  for (size_t base = 0; base < (size_t)n; base += MAXT) {
-    const int m = (int)std::min<size_t>(MAXT, n - base);
+  for_each_batch(n, every_table, [&](const int* ks, int m) {
     int nm = 1;
-    for (int i = 0; i < m; ++i) nm = std::max(nm, nmax[base + i]);
+    for (int i = 0; i < m; ++i) nm = std::max(nm, nmax[ks[i]]);
     dim3 grid((unsigned)std::max(1, std::min((nm + 3) / 4, 2048)), m);
     CountSet zero;     // stays null (nothing zeroed) when own_seg is none of the segments
     for (int sg = 0; sg < segs; ++sg) {
       SdpApplySet s;
       for (int i = 0; i < m; ++i) {
-        const int k = (int)base + i;
+        const int k = ks[i];
         const bool own = sg == own_seg;
         s.t[i] = SdpApply{W[k], seg_ids[sg * n + k], seg_g[sg * n + k], seg_count[sg * n + k], D[k], own ? slot[k] : nullptr,
                           own ? own_count[k] : nullptr};
@@ -1259,7 +1142,7 @@ extern "C" void fm_sdp_apply_segments(int n, int segs, int own_seg, float* const
       hipLaunchKernelGGL(fm_sdp_apply, grid, dim3(256), 0, st, s, lr, nm);
     }
     if (own_seg >= 0 && own_seg < segs) hipLaunchKernelGGL(fm_emb_zero_counts, dim3(1), dim3(64), 0, st, zero);
-  }
+  });
 }
 
 // ---- Adagrad apply launchers ------------------------------------------------------------------
@@ -1271,14 +1154,12 @@ static void launch_adagrad_apply(void (*kernel)(AdaSet, const float*, float), bo
                                  float* const* H, const int* D, const int* const* ids, const float* const* g,
                                  int* const* count, int* const* slot, const int* nmax, const float* lr, float eps,
                                  hipStream_t st) {
-  if (n <= 0) return;
-  for (size_t base = 0; base < (size_t)n; base += MAXT) {
-    const int m = (int)std::min<size_t>(MAXT, n - base);
+  for_each_batch(n, every_table, [&](const int* ks, int m) {
     AdaSet s;
     CountSet zero;
     int nm = 1;
     for (int i = 0; i < m; ++i) {
-      const int k = (int)base + i;
+      const int k = ks[i];
       const uintptr_t a = ((uintptr_t)W[k]) | ((uintptr_t)g[k]) | (h_vec ? (uintptr_t)H[k] : 0);
       const bool vec = D[k] % 4 == 0 && (a & 15) == 0;
       s.t[i] = AdaDesc{W[k], H[k], ids[k], g[k], count[k], slot[k], D[k], nmax[k], vec ? 1 : 0};
@@ -1290,7 +1171,7 @@ static void launch_adagrad_apply(void (*kernel)(AdaSet, const float*, float), bo
     dim3 grid((unsigned)std::max(1, std::min((nm + 7) / 8, 2048)), m);
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, s, lr, eps);
     hipLaunchKernelGGL(fm_emb_zero_counts, dim3(1), dim3(64), 0, st, zero);
-  }
+  });
 }
 
 extern "C" void fm_emb_adagrad_apply(int n, float* const* W, float* const* H, const int* D, const int* const* ids,
@@ -1314,14 +1195,12 @@ extern "C" void fm_sdp_rowwise_merge_segments(int n, int segs, const int* rows, 
                                               const int* const* own_ids, int* const* own_count, int* const* slot,
                                               int* const* mids, float* const* mg, int* const* mcount, const int* nmax,
                                               const int* mcap, hipStream_t st) {
-  if (n <= 0) return;
-  for (size_t base = 0; base < (size_t)n; base += MAXT) {
-    const int m = (int)std::min<size_t>(MAXT, n - base);
+  for_each_batch(n, every_table, [&](const int* ks, int m) {
     int nm = 1;
     RwReleaseSet rs;
     CountSet zero;
     for (int i = 0; i < m; ++i) {
-      const int k = (int)base + i;
+      const int k = ks[i];
       rs.t[i] = RwRelease{own_ids[k], own_count[k], slot[k], rows[k], nmax[k]};
       zero.c[i] = own_count[k];
       nm = std::max(nm, nmax[k]);
@@ -1334,7 +1213,7 @@ extern "C" void fm_sdp_rowwise_merge_segments(int n, int segs, const int* rows, 
     for (int sg = 0; sg < segs; ++sg) {
       RwMergeSet s;
       for (int i = 0; i < m; ++i) {
-        const int k = (int)base + i;
+        const int k = ks[i];
         const float* gs = seg_g[sg * n + k];
         const bool vec = D[k] % 4 == 0 && ((((uintptr_t)gs) | ((uintptr_t)mg[k])) & 15) == 0;
         s.t[i] = RwMerge{seg_ids[sg * n + k], gs, seg_count[sg * n + k], slot[k], mids[k], mg[k], mcount[k],
@@ -1343,5 +1222,5 @@ extern "C" void fm_sdp_rowwise_merge_segments(int n, int segs, const int* rows, 
       s.n = m;
       hipLaunchKernelGGL(fm_sdp_rowwise_merge, grid, dim3(256), 0, st, s);
     }
-  }
+  });
 }

@@ -61,7 +61,6 @@ void fm_embedding_fwd_multi(int n, const float* const* W, const void* const* idx
                             const float* scale, int out_bf16, long B, hipStream_t st);
 void fm_embedding_set_fwd_mode(int mode);
 void fm_embedding_fwd_last_form(int* out);
-void fm_embedding_set_bwd_mode(int count);
 // claim, optional per table: owner (int32 [rows], -1 filled), dups (int32 [B * bag]), ndup (int32 [1])
 void fm_embedding_bwd_multi(int n, float* const* W, const void* const* idx, const int* idx64, const void* const* dy,
                             const long* ldg, const long* lo, const int* rows, const int* D, const int* bag,

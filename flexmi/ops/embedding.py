@@ -500,13 +500,6 @@ class Embedding(Op):
     # tables off the atomic kernel, 1.162-1.163 vs 1.171 ms/step at ratio 1
     # (profiles/bench_ab_claim_ratio_r5cr.txt)
     CLAIM_RATIO = 0.2
-    # the count / update kernel pair (csrc/kernels/embedding.hip, fm_embedding_set_bwd_mode(1)) for
-    # every table above the tiny-table LDS kernel's rows, on the same slot / flag buffers: an
-    # alternative form kept tested (tests/test_gpu_kernels.py), off by default
-    COUNT = False
-    # the wave-private LDS kernel's table-size limit: the same constant as the C++ dispatcher
-    # (embedding.hip kind_of TINY_ROWS)
-    TINY_ROWS = 64
 
     def _claim_buffers(self, ctx):
         """Owner-computes sparse SGD buffers for a mostly-unique table (rows > lookups per step):
@@ -517,7 +510,7 @@ class Embedding(Op):
         s = ctx.saved
         if "claim" not in s:
             w, idx = ctx.weights[0], ctx.inputs[0]
-            big = w.shape[0] > (Embedding.TINY_ROWS if Embedding.COUNT else Embedding.CLAIM_RATIO * idx.numel())
+            big = w.shape[0] > Embedding.CLAIM_RATIO * idx.numel()
             if big and self.out_dim % 4 == 0:
                 dev = w.device
                 s["claim"] = (torch.full((w.shape[0],), -1, dtype=torch.int32, device=dev),

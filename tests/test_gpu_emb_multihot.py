@@ -157,6 +157,26 @@ def test_mode2_on_uniform_sets_equals_su_and_split(gpu, fwd_mode, out_dt):
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("out_dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("idx_dt", [torch.int64, torch.int32])
+@pytest.mark.parametrize("bag,form", [(1, "multi_su"), (11, "multi"), (20, "split")])
+def test_uniform_forms_on_batches_that_end_inside_a_block_iteration(gpu, fwd_mode, bag, form, idx_dt, out_dt):
+    """The per-table-grid forms share their lookup loops (emb_bal_short, emb_gather_sum): B = 37 and
+    B = 2085 are no multiple of the samples a block iteration covers at D = 128 or D = 64 (8 / 16 lane
+    groups, times four samples in the single-lookup loop, over 1 to 4 groups per sample in the split
+    kernel), so the clamped loads and the b >= B exits run.  A bag of 11 is one eight-wide gather
+    and a tail of three; every set holds an index of -1 and one past the table, and a row shard."""
+    from flexmi.ops import _kernels as Kk
+    fwd_mode(0)
+    for B in (37, 2085):
+        for D in (128, 64):
+            s = _Set(gpu, B, [_spec(5000, D, bag, dt=idx_dt), _spec(3000, D, bag, lo=1000, dt=idx_dt, scale=0.5)],
+                     seed=B + D + bag)
+            got = s.run(out_dt)
+            assert Kk.embedding_fwd_last_form() == form, (B, D)
+            s.check(got, out_dt)
+
+
 @pytest.mark.parametrize("B", [5, 1])
 def test_descriptor_batches_of_32(gpu, fwd_mode, B):
     """34 tables: a launch set of 32 and one of 2, both with unequal bags."""

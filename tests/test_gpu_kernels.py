@@ -485,10 +485,12 @@ def test_embedding_owner_computes_duplicate_heavy(gpu, dy_dtype):
 
 @pytest.mark.parametrize("dy_dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("idx_dtype", [torch.int64, torch.int32])
-def test_embedding_count_update_sgd(gpu, idx_dtype, dy_dtype):
-    """Count / update sparse SGD (FM_EMB_BWD=count: slot = lookups - 1, plain RMW for single-lookup
-    rows, atomics for repeated rows) on every table above 16 rows, incl. a row shard, over three
-    steps: matches the dense reference and leaves every slot free (-1) after each step."""
+def test_embedding_owner_computes_every_table_size(gpu, idx_dtype, dy_dtype):
+    """Claim buffers for every table above 16 rows drive the default claim / dup / owner kernels through a
+    400 000-row table, duplicate-heavy 1500- and 5000-row tables (most lookups take the dup-atomic
+    path), a 40-row table and a row shard (lo = 10000), with both index widths and gradient types, beside
+    a 3-row table on the tiny kernel, over three steps: matches the dense reference and leaves every
+    claim slot free (-1) and every duplicate counter zero after each step."""
     from flexmi.ops import _kernels as Kk
     torch.manual_seed(9)
     B = 2000
@@ -507,26 +509,22 @@ def test_embedding_count_update_sgd(gpu, idx_dtype, dy_dtype):
         else:
             claim += [None, None, None]
     lr = torch.tensor([0.05], device=gpu)
-    Kk.C().embedding_set_bwd_mode(True)
-    try:
-        for step in range(3):
-            dys = [torch.randn(B, D, device=gpu).to(dy_dtype) for _, _, D, _ in specs]
-            Kk.C().embedding_bwd_multi(tables, idxs, dys, [d.stride(0) for d in dys], [1.0] * len(specs), lr, claim,
-                                       los)
-            for k, ((rows, bag, D, lo), W) in enumerate(zip(specs, refs)):
-                flat = idxs[k].reshape(-1).long() - lo
-                keep = (flat >= 0) & (flat < rows)
-                upd = torch.zeros_like(W)
-                upd.index_add_(0, flat[keep], dys[k].float().repeat_interleave(bag, 0)[keep])
-                W -= 0.05 * upd
-            torch.cuda.synchronize()
-            for k in range(len(specs)):
-                assert torch.allclose(tables[k], refs[k], atol=1e-4), (step, specs[k])
-            for k in range(0, len(claim), 3):
-                if claim[k] is not None:
-                    assert int((claim[k] != -1).sum()) == 0, ("slots not freed", step, k // 3)
-    finally:
-        Kk.C().embedding_set_bwd_mode(False)
+    for step in range(3):
+        dys = [torch.randn(B, D, device=gpu).to(dy_dtype) for _, _, D, _ in specs]
+        Kk.C().embedding_bwd_multi(tables, idxs, dys, [d.stride(0) for d in dys], [1.0] * len(specs), lr, claim, los)
+        for k, ((rows, bag, D, lo), W) in enumerate(zip(specs, refs)):
+            flat = idxs[k].reshape(-1).long() - lo
+            keep = (flat >= 0) & (flat < rows)
+            upd = torch.zeros_like(W)
+            upd.index_add_(0, flat[keep], dys[k].float().repeat_interleave(bag, 0)[keep])
+            W -= 0.05 * upd
+        torch.cuda.synchronize()
+        for k in range(len(specs)):
+            assert torch.allclose(tables[k], refs[k], atol=1e-4), (step, specs[k])
+        for k in range(0, len(claim), 3):
+            if claim[k] is not None:
+                assert int((claim[k] != -1).sum()) == 0, ("slots not freed", step, k // 3)
+                assert int(claim[k + 2].item()) == 0, ("duplicate counter not zeroed", step, k // 3)
 
 
 @pytest.mark.parametrize("dy_dtype", [torch.float32, torch.bfloat16])
