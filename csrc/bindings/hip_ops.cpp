@@ -735,8 +735,23 @@ void cast_bf16(torch::Tensor src, torch::Tensor dst) { fm_cast_bf16(src.data_ptr
 
 void loss(int64_t loss_type, torch::Tensor logits, torch::Tensor labels, c10::optional<torch::Tensor> grad, double scale,
           torch::Tensor acc, int64_t mask, double clamp_t) {
+  auto act = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.is_contiguous() && (t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32);
+  };
+  TORCH_CHECK(logits.dim() >= 1 && act(logits), "loss: contiguous bf16 or fp32 device logits");
+  TORCH_CHECK(!given(grad) || (act(*grad) && grad->numel() == logits.numel()),
+              "loss: grad must be a contiguous bf16 or fp32 device tensor of the logits' size");
   long B = logits.size(0);
   int C = (int)(logits.numel() / std::max<long>(1, B));
+  if (loss_type == 51) {   // sparse categorical cross-entropy: the kernel reads one int per row
+    TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() && labels.scalar_type() == torch::kInt32 && labels.numel() == B,
+                "loss: sparse labels must be a contiguous int32 device tensor with one entry per row");
+  } else {
+    TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() && labels.scalar_type() == torch::kFloat32 &&
+                    labels.numel() == logits.numel(), "loss: labels must be a contiguous fp32 device tensor of the logits' size");
+  }
+  TORCH_CHECK(acc.is_cuda() && acc.is_contiguous() && acc.scalar_type() == torch::kFloat32 && acc.numel() >= 8,
+              "loss: acc must be a contiguous fp32 device tensor of at least 8 slots");
   int gb = given(grad) ? is_bf16(*grad) : 0;
   fm_loss_fwd_bwd(logits.data_ptr(), is_bf16(logits), labels.data_ptr(), mptr(grad), gb, B, C, (int)loss_type, (float)scale,
                   acc.data_ptr<float>(), (int)mask, (float)clamp_t, cur());
@@ -760,39 +775,57 @@ void auc_hist(torch::Tensor scores, torch::Tensor labels, torch::Tensor hist, to
                       (int)std::max<int64_t>(-1, std::min<int64_t>(rounds, 64)), cur());
 }
 
-void unary_fwd(int64_t code, torch::Tensor x, torch::Tensor y) { fm_unary_forward((int)code, x.data_ptr(), y.data_ptr(), x.numel(), is_bf16(x), cur()); }
-void unary_bwd(int64_t code, torch::Tensor x, torch::Tensor y, torch::Tensor dy, torch::Tensor dx, bool acc) {
-  fm_unary_backward((int)code, x.data_ptr(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), acc, is_bf16(x), cur());
-}
-// relu: y = relu(a op b); ymask (backward): the incoming gradient is zeroed where ymask <= 0
-void binary_fwd(int64_t code, torch::Tensor a, torch::Tensor b, torch::Tensor y, bool relu) {
-  TORCH_CHECK(a.numel() == b.numel() && a.numel() == y.numel() && a.scalar_type() == b.scalar_type() &&
-                  a.scalar_type() == y.scalar_type(), "binary_fwd: same-size same-dtype operands");
-  fm_binary_forward((int)code, a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), relu ? 1 : 0, is_bf16(a), cur());
-}
-void binary_bwd(int64_t code, torch::Tensor a, torch::Tensor b, torch::Tensor dy, c10::optional<torch::Tensor> ymask,
-                c10::optional<torch::Tensor> da, c10::optional<torch::Tensor> db, bool acca, bool accb) {
-  TORCH_CHECK(dy.numel() == a.numel() && dy.numel() == b.numel() && dy.scalar_type() == a.scalar_type(), "binary_bwd: operands");
-  if (given(ymask))
-    TORCH_CHECK(ymask->numel() == dy.numel() && ymask->scalar_type() == dy.scalar_type(), "binary_bwd: ymask");
-  fm_binary_backward((int)code, a.data_ptr(), b.data_ptr(), dy.data_ptr(), cptr(ymask), mptr(da), mptr(db), a.numel(), acca,
-                     accb, is_bf16(a), cur());
-}
-// DCNv2 cross combine (cross.hip).  The kernels index every operand as a flat array of ref's length:
-// each one given must be a contiguous device tensor of ref's dtype and element count
-static void cross_operand(const torch::Tensor& ref, const c10::optional<torch::Tensor>& t, const char* what) {
+// The element-wise and cross kernels index every operand as a flat array of ref's length: each one
+// given must be a contiguous device tensor of ref's dtype and element count
+static void flat_operand(const torch::Tensor& ref, const c10::optional<torch::Tensor>& t, const char* what) {
   if (!given(t)) return;
   TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == ref.scalar_type() && t->numel() == ref.numel(), what,
               ": contiguous device tensor of the first operand's dtype and size expected");
 }
+static void flat_first(const torch::Tensor& ref, const char* what) {
+  TORCH_CHECK(ref.is_cuda() && ref.is_contiguous() &&
+                  (ref.scalar_type() == torch::kBFloat16 || ref.scalar_type() == torch::kFloat32),
+              what, ": contiguous bf16 or fp32 device tensors");
+}
+void unary_fwd(int64_t code, torch::Tensor x, torch::Tensor y) {
+  flat_first(x, "unary_fwd");
+  flat_operand(x, y, "unary_fwd y");
+  fm_unary_forward((int)code, x.data_ptr(), y.data_ptr(), x.numel(), is_bf16(x), cur());
+}
+void unary_bwd(int64_t code, torch::Tensor x, torch::Tensor y, torch::Tensor dy, torch::Tensor dx, bool acc) {
+  flat_first(x, "unary_bwd");
+  flat_operand(x, y, "unary_bwd y");
+  flat_operand(x, dy, "unary_bwd dy");
+  flat_operand(x, dx, "unary_bwd dx");
+  fm_unary_backward((int)code, x.data_ptr(), y.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), acc, is_bf16(x), cur());
+}
+// relu: y = relu(a op b); ymask (backward): the incoming gradient is zeroed where ymask <= 0
+void binary_fwd(int64_t code, torch::Tensor a, torch::Tensor b, torch::Tensor y, bool relu) {
+  flat_first(a, "binary_fwd");
+  flat_operand(a, b, "binary_fwd b");
+  flat_operand(a, y, "binary_fwd y");
+  fm_binary_forward((int)code, a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), relu ? 1 : 0, is_bf16(a), cur());
+}
+void binary_bwd(int64_t code, torch::Tensor a, torch::Tensor b, torch::Tensor dy, c10::optional<torch::Tensor> ymask,
+                c10::optional<torch::Tensor> da, c10::optional<torch::Tensor> db, bool acca, bool accb) {
+  flat_first(a, "binary_bwd");
+  flat_operand(a, b, "binary_bwd b");
+  flat_operand(a, dy, "binary_bwd dy");
+  flat_operand(a, ymask, "binary_bwd ymask");
+  flat_operand(a, da, "binary_bwd da");
+  flat_operand(a, db, "binary_bwd db");
+  fm_binary_backward((int)code, a.data_ptr(), b.data_ptr(), dy.data_ptr(), cptr(ymask), mptr(da), mptr(db), a.numel(), acca,
+                     accb, is_bf16(a), cur());
+}
+// DCNv2 cross combine (cross.hip): operands checked by flat_operand above
 // y = x0 * t + x; without x (the first layer, x_l = x_0): y = x0 * t + x0
 void cross_fwd(torch::Tensor x0, torch::Tensor t, c10::optional<torch::Tensor> x, torch::Tensor y) {
   TORCH_CHECK(x0.is_cuda() && x0.is_contiguous() &&
                   (x0.scalar_type() == torch::kBFloat16 || x0.scalar_type() == torch::kFloat32),
               "cross_fwd: contiguous bf16 or fp32 device tensors");
-  cross_operand(x0, t, "cross_fwd t");
-  cross_operand(x0, x, "cross_fwd x");
-  cross_operand(x0, y, "cross_fwd y");
+  flat_operand(x0, t, "cross_fwd t");
+  flat_operand(x0, x, "cross_fwd x");
+  flat_operand(x0, y, "cross_fwd y");
   fm_cross_forward(x0.data_ptr(), t.data_ptr(), cptr(x), y.data_ptr(), x0.numel(), is_bf16(x0), cur());
 }
 // dt (+)= dy * x0, dx0 (+)= dy * t (+ dy when self: the form without x), dx (+)= dy; absent outputs are skipped
@@ -801,11 +834,11 @@ void cross_bwd(torch::Tensor dy, torch::Tensor x0, torch::Tensor t, c10::optiona
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() &&
                   (dy.scalar_type() == torch::kBFloat16 || dy.scalar_type() == torch::kFloat32),
               "cross_bwd: contiguous bf16 or fp32 device tensors");
-  cross_operand(dy, x0, "cross_bwd x0");
-  cross_operand(dy, t, "cross_bwd t");
-  cross_operand(dy, dt, "cross_bwd dt");
-  cross_operand(dy, dx0, "cross_bwd dx0");
-  cross_operand(dy, dx, "cross_bwd dx");
+  flat_operand(dy, x0, "cross_bwd x0");
+  flat_operand(dy, t, "cross_bwd t");
+  flat_operand(dy, dt, "cross_bwd dt");
+  flat_operand(dy, dx0, "cross_bwd dx0");
+  flat_operand(dy, dx, "cross_bwd dx");
   TORCH_CHECK(!(self && mptr(dx)), "cross_bwd: the form without x has no dx");
   fm_cross_backward(dy.data_ptr(), x0.data_ptr(), t.data_ptr(), mptr(dt), mptr(dx0), mptr(dx), dy.numel(), acct, acc0, accx,
                     self, is_bf16(dy), cur());
@@ -1323,18 +1356,27 @@ void pad_rows(torch::Tensor src, torch::Tensor dst, int64_t K, int64_t n, int64_
 
 // ----------------------------------------------------------------------------- LSTM
 static float* fp(torch::Tensor& t, int64_t off) {
-  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && off >= 0 && off < t.numel(), "lstm: fp32 buffer/offset");
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kFloat32 && off >= 0 && off < t.numel(),
+              "lstm: contiguous fp32 device buffer/offset");
   return t.data_ptr<float>() + off;
 }
 // activation-dtype (bf16 or fp32) buffer at an element offset
 static void* bp(torch::Tensor& t, int64_t off) {
-  TORCH_CHECK((t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32) && off >= 0 && off < t.numel(),
-              "lstm: bf16/fp32 buffer/offset");
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && (t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32) &&
+                  off >= 0 && off < t.numel(), "lstm: contiguous bf16/fp32 device buffer/offset");
   return (char*)t.data_ptr() + t.element_size() * off;
+}
+// an optional [B, H] tensor of the activation dtype (that of ref)
+static void lstm_act(const torch::Tensor& ref, const c10::optional<torch::Tensor>& t, int64_t n, const char* what) {
+  if (!given(t)) return;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == ref.scalar_type() && t->numel() >= n, what,
+              ": contiguous device tensor of the activation dtype with B*H elements expected");
 }
 void lstm_init(c10::optional<torch::Tensor> h0, c10::optional<torch::Tensor> c0, torch::Tensor hprev, int64_t ldhp,
                torch::Tensor cinit, int64_t B, int64_t H) {
   TORCH_CHECK(hprev.numel() >= (B - 1) * ldhp + H && cinit.numel() >= B * H, "lstm_init: sizes");
+  lstm_act(hprev, h0, B * H, "lstm_init h0");
+  lstm_act(hprev, c0, B * H, "lstm_init c0");
   fm_lstm_init(cptr(h0), cptr(c0), bp(hprev, 0), ldhp, fp(cinit, 0), B, H, is_bf16(hprev), cur());
 }
 void lstm_cell_fwd(torch::Tensor G, int64_t g_off, int64_t ldg, torch::Tensor cprev, int64_t cp_off, int64_t ldcp,
@@ -1342,7 +1384,12 @@ void lstm_cell_fwd(torch::Tensor G, int64_t g_off, int64_t ldg, torch::Tensor cp
                    torch::Tensor hprev, int64_t hp_off, int64_t ldhp, c10::optional<torch::Tensor> hT,
                    c10::optional<torch::Tensor> cT, int64_t B, int64_t H) {
   TORCH_CHECK(g_off + (B - 1) * ldg + 4 * H <= G.numel() && c_off + (B - 1) * ldc + H <= cout.numel() &&
-                  y_off + (B - 1) * ldy + H <= y.numel(), "lstm_cell_fwd: extents");
+                  y_off + (B - 1) * ldy + H <= y.numel() && cp_off + (B - 1) * ldcp + H <= cprev.numel(),
+              "lstm_cell_fwd: extents");
+  TORCH_CHECK(hp_off < 0 || (hprev.scalar_type() == y.scalar_type() && hp_off + (B - 1) * ldhp + H <= hprev.numel()),
+              "lstm_cell_fwd: Hp must have y's dtype and hold step t+1");
+  lstm_act(y, hT, B * H, "lstm_cell_fwd hT");
+  lstm_act(y, cT, B * H, "lstm_cell_fwd cT");
   void* hn = hp_off >= 0 ? bp(hprev, hp_off) : nullptr;
   fm_lstm_cell_fwd(fp(G, g_off), ldg, fp(cprev, cp_off), ldcp, fp(cout, c_off), ldc, bp(y, y_off), ldy, hn, ldhp, mptr(hT),
                    mptr(cT), B, H, is_bf16(y), cur());
@@ -1352,7 +1399,8 @@ void lstm_cell_bwd(torch::Tensor A, int64_t a_off, int64_t lda, torch::Tensor ct
                    int64_t ldy, torch::Tensor dh, torch::Tensor dc, torch::Tensor dG, int64_t dg_off, int64_t lddg,
                    int64_t B, int64_t H) {
   TORCH_CHECK(a_off + (B - 1) * lda + 4 * H <= A.numel() && dg_off + (B - 1) * lddg + 4 * H <= dG.numel() &&
-                  dh.numel() >= B * H && dc.numel() >= B * H, "lstm_cell_bwd: extents");
+                  dh.numel() >= B * H && dc.numel() >= B * H && ct_off + (B - 1) * ldc + H <= ct.numel() &&
+                  cp_off + (B - 1) * ldcp + H <= cprev.numel(), "lstm_cell_bwd: extents");
   const void* dyp = nullptr;
   if (given(dy)) {
     TORCH_CHECK(dy_off + (B - 1) * ldy + H <= dy->numel() && dy->scalar_type() == dG.scalar_type(), "lstm_cell_bwd: dy extent");

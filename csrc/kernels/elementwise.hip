@@ -19,7 +19,7 @@ FM_DEVICE float un_f(int code, float x) {
     case 0: return x > 0.f ? x : 0.f;
     case 1: return 1.f / (1.f + __expf(-x));
     case 2: return tanhf(x);
-    case 3: return x > 0.f ? x : (__expf(x) - 1.f);
+    case 3: return x > 0.f ? x : expm1f(x);   // exp(x) - 1 cancels near 0 (22 % off at x = -1.5e-7)
     default: return __expf(x);
   }
 }
@@ -27,7 +27,7 @@ FM_DEVICE float un_b(int code, float x, float y, float dy) {
   switch (code) {
     case 0: return x > 0.f ? dy : 0.f;
     case 1: return dy * y * (1.f - y);
-    case 2: return dy * (1.f - y * y);
+    case 2: return dy * fmaf(-y, y, 1.f);   // one rounding: 1 - y*y in two loses the result where |y| -> 1
     case 3: return x > 0.f ? dy : dy * (y + 1.f);
     default: return dy * y;
   }

@@ -3,6 +3,9 @@
 // atomicAdd per sample per metric).  One pass over the logits computes dL/dlogit = scale*(p - y)
 // and accumulates all requested metrics; each block reduces in registers/LDS and issues 8 atomics.
 // Slots: 0 all, 1 correct, 2 cce, 3 sparse cce, 4 mse, 5 rmse, 6 mae, 7 loss value.
+// Slots 1-6 are added only under mask bits 0-5 (metrics_mask() in flexmi/core/loss_metrics.py; the
+// same contract as loss_and_metrics_torch and csrc/cpu/init_metrics.cc); slot 3 is -log p[argmax y]
+// for any label form.
 // clamp_t in (0, 0.5): DLRM --loss-threshold -- predictions are clamped to [t, 1-t] before the
 // loss and metrics, and clamped predictions pass no gradient (reference dlrm.cc:129 left it a TODO).
 #include "common.h"
@@ -12,9 +15,13 @@ namespace {
 enum { LOSS_CCE = 50, LOSS_SCCE = 51, LOSS_MSE_AVG = 52, LOSS_MSE_SUM = 53, LOSS_BCE = 54 };
 constexpr float LOG_MIN = 1e-7f;
 
+// v: a thread's eight slot sums.  Slot s in 1..6 is dropped here unless mask bit s-1 is set.
 template <typename T>
-FM_DEVICE void block_accumulate(float (&v)[8], float* acc) {
+FM_DEVICE void block_accumulate(float (&v)[8], float* acc, int mask) {
   __shared__ float red[8][4];
+#pragma unroll
+  for (int s = 1; s < 7; ++s)
+    if (!((mask >> (s - 1)) & 1)) v[s] = 0.f;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
@@ -44,7 +51,7 @@ __global__ void __launch_bounds__(256) fm_loss_kernel(const LT* __restrict__ log
     const float* yp = sparse ? nullptr : reinterpret_cast<const float*>(labels) + b * C;
     float best = -3.4e38f, besty = -3.4e38f;
     int bi = 0x7fffffff, byi = 0x7fffffff;
-    float se = 0.f, ae = 0.f, cce = 0.f, lossv = 0.f, plab = 1.f;
+    float se = 0.f, ae = 0.f, cce = 0.f, lossv = 0.f;
     for (int c = lane; c < C; c += 64) {
       float p = ld<LT>(lp + c);
       bool clipped = false;
@@ -61,7 +68,6 @@ __global__ void __launch_bounds__(256) fm_loss_kernel(const LT* __restrict__ log
       if (y > 0.f) cce += -y * __logf(fmaxf(p, LOG_MIN));
       if (p > best || (p == best && c < bi)) { best = p; bi = c; }
       if (y > besty || (y == besty && c < byi)) { besty = y; byi = c; }
-      if (c == lab) plab = p;
       if (loss_type == LOSS_BCE) {
         float pc = fminf(fmaxf(p, LOG_MIN), 1.f - LOG_MIN);
         lossv += -(y * __logf(pc) + (1.f - y) * __logf(1.f - pc));
@@ -80,7 +86,6 @@ __global__ void __launch_bounds__(256) fm_loss_kernel(const LT* __restrict__ log
       float oy = __shfl_xor(besty, o, 64);
       int oyi = __shfl_xor(byi, o, 64);
       if (oy > besty || (oy == besty && oyi < byi)) { besty = oy; byi = oyi; }
-      plab = fminf(plab, __shfl_xor(plab, o, 64));
     }
     if (lane == 0) {
       v[0] += 1.f;
@@ -91,16 +96,23 @@ __global__ void __launch_bounds__(256) fm_loss_kernel(const LT* __restrict__ log
         v[1] += ok ? 1.f : 0.f;
       }
       v[2] += cce;
-      if (sparse) v[3] += -__logf(fmaxf(plab, LOG_MIN));
+      // -log p[argmax y]: byi is the label for sparse labels (the one y = 1), the first maximum otherwise
+      float scce = 0.f;
+      if ((mask & 4) || sparse) {
+        float pl = ld<LT>(lp + (byi < C ? byi : 0));
+        if (clamp_t > 0.f) pl = fminf(fmaxf(pl, clamp_t), 1.f - clamp_t);
+        scce = -__logf(fmaxf(pl, LOG_MIN));
+      }
+      v[3] += scce;
       v[4] += se;
       v[5] += sqrtf(se);
       v[6] += ae;
       if (loss_type == LOSS_BCE) v[7] += lossv;
-      else if (loss_type == LOSS_CCE || loss_type == LOSS_SCCE) v[7] += sparse ? -__logf(fmaxf(plab, LOG_MIN)) : cce;
+      else if (loss_type == LOSS_CCE || loss_type == LOSS_SCCE) v[7] += sparse ? scce : cce;
       else v[7] += se;
     }
   }
-  block_accumulate<float>(v, acc);
+  block_accumulate<float>(v, acc, mask);
 }
 
 // thread per row (C == 1, e.g. DLRM click probability)
@@ -122,7 +134,9 @@ __global__ void __launch_bounds__(256) fm_loss1_kernel(const LT* __restrict__ lo
     float d = p - y;
     v[0] += 1.f;
     v[1] += ((p >= 0.5f) == (y >= 0.5f)) ? 1.f : 0.f;
-    if (y > 0.f) v[2] += -y * __logf(fmaxf(p, LOG_MIN));
+    const float cce = y > 0.f ? -y * __logf(fmaxf(p, LOG_MIN)) : 0.f;
+    v[2] += cce;
+    if (mask & 4) v[3] += -__logf(fmaxf(p, LOG_MIN));   // argmax over one class is that class
     v[4] += d * d;
     v[5] += fabsf(d);
     v[6] += fabsf(d);
@@ -130,11 +144,10 @@ __global__ void __launch_bounds__(256) fm_loss1_kernel(const LT* __restrict__ lo
       float pc = fminf(fmaxf(p, LOG_MIN), 1.f - LOG_MIN);
       v[7] += -(y * __logf(pc) + (1.f - y) * __logf(1.f - pc));
     } else {
-      v[7] += d * d;
+      v[7] += loss_type == LOSS_CCE ? cce : d * d;
     }
   }
-  if (!(mask & 1)) v[1] = 0.f;
-  block_accumulate<float>(v, acc);
+  block_accumulate<float>(v, acc, mask);
 }
 
 }  // namespace

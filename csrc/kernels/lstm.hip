@@ -71,12 +71,12 @@ __global__ void fm_lstm_cell_bwd_kernel(const float* __restrict__ A, long lda, c
     const float c = c_t[b * ldc + j];
     const float tc = tanhf(c);
     const float dht = dh[i] + (dy ? tof(dy[b * ldy + j]) : 0.f);
-    const float dct = dc[i] + dht * og * (1.f - tc * tc);
+    const float dct = dc[i] + dht * og * fmaf(-tc, tc, 1.f);   // 1 - tanh^2 in one rounding
     const float cp = c_prev[b * ldcp + j];
     T* d = dG + b * lddg;
     d[j] = fromf<T>(dct * gg * ig * (1.f - ig));
     d[H + j] = fromf<T>(dct * cp * fg * (1.f - fg));
-    d[2 * H + j] = fromf<T>(dct * ig * (1.f - gg * gg));
+    d[2 * H + j] = fromf<T>(dct * ig * fmaf(-gg, gg, 1.f));
     d[3 * H + j] = fromf<T>(dht * tc * og * (1.f - og));
     dc[i] = dct * fg;
   }

@@ -100,6 +100,12 @@ def metrics_mask(metrics):
     return mask
 
 
+# Sums the executor asks of every backend whether or not their metric was requested: they fall out of
+# the pass that computes the gradient, and PerfMetrics.get_mse() and the like read them unasked.
+# Accuracy and sparse CCE (an argmax each) stay on request.
+ALWAYS_SUMMED = (1 << 1) | (1 << 3) | (1 << 4) | (1 << 5)      # cce, mse, rmse, mae
+
+
 def wants_auc(metrics):
     return any(int(m) == int(MetricsType.METRICS_AUC) for m in (metrics or []))
 
@@ -228,4 +234,5 @@ class Metrics:
         self.loss_type = LossType(loss_type)
         self.metrics = list(metrics or [])
         self.mask = metrics_mask(self.metrics)
+        self.kernel_mask = self.mask | ALWAYS_SUMMED      # what the loss pass is asked to accumulate
         self.auc = wants_auc(self.metrics)     # not a kernel mask bit: a histogram pass of its own

@@ -336,6 +336,7 @@ class FFModel:
         self.loss_type = LossType(loss_type) if loss_type is not None else LossType.LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE
         self.loss_op = Loss(self.loss_type)
         self.metrics_op = Metrics(self.loss_type, metrics or [])
+        self._refuse_duplicate_inputs()
         # ---- strategy --------------------------------------------------------
         from flexmi.parallel import strategy as S
         cfg = self.config
@@ -364,6 +365,20 @@ class FFModel:
                 raise ValueError(f"METRICS_AUC needs one score per sample and a float label; this model's output is "
                                  f"{tuple(final.dims)} with loss {self.loss_type.name}")
         return self
+
+    def _refuse_duplicate_inputs(self):
+        """One tensor at two inputs of one op: both gradients land in one buffer.  The element-wise
+        binary ops handle that (the second slot accumulates, in a launch of its own on HIP); every
+        other op with several data inputs (Concat, BatchMatmul, DotInteraction, CrossCombine, LSTM)
+        writes its input gradients in one launch, where a store and an accumulate into the same
+        buffer would race, so such a graph is refused instead of trained with a wrong gradient."""
+        from flexmi.ops.elementwise import ElementBinary
+        for op in self.layers:
+            guids = [t.guid for t in op.inputs]
+            if len(set(guids)) != len(guids) and not isinstance(op, ElementBinary):
+                slots = [i for i, g in enumerate(guids) if guids.count(g) > 1]
+                raise ValueError(f"{type(op).__name__} '{op.name}' reads one tensor at inputs {slots}: its backward "
+                                 f"cannot add two gradients into one buffer (only the element-wise binary ops can)")
 
     def init_layers(self):
         """``FFModel::init_layers``: build the per-rank executor (allocation + weight init)."""

@@ -119,12 +119,15 @@ class ElementBinary(Op):
         db = ctx.in_grads[1] if len(ctx.in_grads) > 1 else None
         if ctx.hip:
             fused = ctx.saved.get("fused_relu")
-            if fused is not None:
-                K.binary_backward(self.code, a, b, fused[1], da, db, ctx.in_grad_accumulate[0], ctx.in_grad_accumulate[1],
-                                  ymask=fused[0])
+            g, ymask = (fused[1], fused[0]) if fused is not None else (dy, None)
+            acca, accb = ctx.in_grad_accumulate[0], ctx.in_grad_accumulate[1]
+            if da is not None and db is not None and da.data_ptr() == db.data_ptr():
+                # op(t, t): both gradients go to t's buffer.  The kernel's outputs are __restrict__,
+                # so each gets a launch of its own, the second adding to the first
+                K.binary_backward(self.code, a, b, g, da, None, acca, False, ymask=ymask)
+                K.binary_backward(self.code, a, b, g, None, db, False, True, ymask=ymask)
                 return
-            K.binary_backward(self.code, a, b, dy, da, db,
-                              ctx.in_grad_accumulate[0], ctx.in_grad_accumulate[1])
+            K.binary_backward(self.code, a, b, g, da, db, acca, accb, ymask=ymask)
             return
         a, b, g = a.float(), b.float(), dy.float()
         if self.code == 0:

@@ -1722,6 +1722,19 @@ class Executor:
         fwd[-1].writes = {t.guid for t in op.outputs}
         fwd[-1].check = (lambda op=op, c=c: self._check_op(op.name + ".fwd", c.outputs, "output"))
 
+    def _acc_flags(self, op, c, written):
+        """Per input slot of ``op``: does its backward add into the gradient buffer (True) or store
+        (False)?  A slot that writes a tensor's home gradient accumulates when an earlier step wrote
+        that buffer, or when an earlier slot of this same op does (one tensor at two inputs)."""
+        flags, mine = [], set()
+        for i, t in enumerate(op.inputs):
+            same = c.in_grads[i] is not None and self.need[(op.guid, i)].same_as(self.home[t.guid])
+            key = self.gkey(t.guid)
+            flags.append(bool(same and (key in written or key in mine)))
+            if same:
+                mine.add(key)
+        return flags
+
     def _compile_backward(self, bwd, C):
         written = set()
         # gradient reductions into a tensor's home grad buffer are started where the consumer's
@@ -1838,10 +1851,7 @@ class Executor:
                 op = st[1]
                 c = self.ctx.get(op.guid)
                 if c is not None:
-                    flags = []
-                    for i, t in enumerate(op.inputs):
-                        same = c.in_grads[i] is not None and self.need[(op.guid, i)].same_as(self.home[t.guid])
-                        flags.append(bool(same and self.gkey(t.guid) in written))
+                    flags = self._acc_flags(op, c, written)
                     for o in op.outputs:
                         if o.guid in self.grad and self.gkey(o.guid) not in written:
                             C(bwd, o.name + ".zero_unused_grad", (lambda t=self.grad[o.guid]: t.zero_()))
@@ -1906,10 +1916,7 @@ class Executor:
         flags = {}
         for op in region_b:
             c = self.ctx[op.guid]
-            fl = []
-            for i, t in enumerate(op.inputs):
-                same = c.in_grads[i] is not None and self.need[(op.guid, i)].same_as(self.home[t.guid])
-                fl.append(bool(same and self.gkey(t.guid) in written))
+            fl = self._acc_flags(op, c, written)
             for o in op.outputs:
                 if o.guid in self.grad and self.gkey(o.guid) not in written:
                     C(bwd, o.name + ".zero_unused_grad", (lambda t=self.grad[o.guid]: t.zero_()))
@@ -2221,7 +2228,7 @@ class Executor:
     def _loss_kernel(self, compute_grad):
         from flexmi.ops import _kernels as K
         scale = 1.0 / self.final.dims[0]
-        mask = self.metrics_obj.mask if self.metrics_obj else 0
+        mask = self.metrics_obj.kernel_mask if self.metrics_obj else 0
         clamp = float(getattr(self.model, "loss_threshold", 0.0) or 0.0)
         if self.backend == "hip":
             K.loss_forward_backward(int(self.loss_type), self.logits_buf, self.label_buf,
