@@ -656,57 +656,89 @@ void strided_copy4(torch::Tensor src, torch::Tensor dst, std::vector<int64_t> d,
   fm_strided_copy4_run(src.data_ptr(), dst.data_ptr(), is_bf16(src), di, sl, tl, so, to, acc ? 1 : 0, cur());
 }
 
+// elements addressable from t's first one: a row view or column slice of a wider buffer may be read
+// and written with that buffer's row stride
+int64_t extent(const torch::Tensor& t) {
+  return (int64_t)(t.storage().nbytes() / t.element_size()) - t.storage_offset();
+}
+
+// a launcher status (launchers.h) that is not 0 launched nothing: raise what it names
+void dot_check(int status) {
+  const char* msg = "";
+  fm_dot_interaction_error(status, &msg);
+  TORCH_CHECK(status == 0, msg);
+}
+
+int64_t dot_block_cap() { return fm_dot_block_cap(); }
+
 void dot_fwd(std::vector<torch::Tensor> zs, int64_t ldz, torch::Tensor out, int64_t ldo, int64_t D, int64_t W, bool self) {
-  TORCH_CHECK(zs.size() >= 1 && zs.size() <= 32, "dot interaction: 1..32 features");
+  TORCH_CHECK(zs.size() >= 1 && zs.size() <= 64, "dot interaction: 1..64 features");
   std::vector<const void*> p;
   long B = out.size(0);
   const auto dt = out.scalar_type();
   TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kFloat32, "dot interaction: bf16 or fp32");
-  TORCH_CHECK(out.numel() >= (B - 1) * ldo + W, "dot output too small");
+  TORCH_CHECK(extent(out) >= (B - 1) * ldo + W, "dot output too small");
   for (auto& z : zs) {
     check_cuda(z, "z");
     TORCH_CHECK(z.scalar_type() == dt, "dot interaction inputs must match the output dtype");
-    TORCH_CHECK(z.numel() >= (B - 1) * ldz + D, "dot input too small");
+    TORCH_CHECK(extent(z) >= (B - 1) * ldz + D, "dot input too small");
     p.push_back(z.data_ptr());
   }
   if (dt == torch::kFloat32) {
     TORCH_CHECK(D % 2 == 0, "dot interaction fp32: even D");
-    fm_dot_interaction_fwd_f32((const float* const*)p.data(), (int)p.size(), ldz, out.data_ptr<float>(), ldo, B, (int)D,
-                               (int)W, self ? 1 : 0, cur());
+    dot_check(fm_dot_interaction_fwd_f32((const float* const*)p.data(), (int)p.size(), ldz, out.data_ptr<float>(), ldo,
+                                         B, (int)D, (int)W, self ? 1 : 0, cur()));
     return;
   }
   TORCH_CHECK(D % 16 == 0 && W % 8 == 0 && ldz % 8 == 0 && ldo % 8 == 0, "dot interaction: D%16, W%8, ld%8");
-  fm_dot_interaction_fwd(p.data(), (int)p.size(), ldz, out.data_ptr(), ldo, B, (int)D, (int)W, self ? 1 : 0, cur());
+  dot_check(fm_dot_interaction_fwd(p.data(), (int)p.size(), ldz, out.data_ptr(), ldo, B, (int)D, (int)W, self ? 1 : 0,
+                                   cur()));
 }
 
 // act0 (fp32 only): activation backward of feature 0's producer applied to dz[0] (10 = none)
 void dot_bwd(std::vector<torch::Tensor> zs, int64_t ldz, torch::Tensor dout, int64_t ldo,
-             std::vector<c10::optional<torch::Tensor>> dzs, int64_t lddz, int64_t acc_mask, int64_t D, bool self,
+             std::vector<c10::optional<torch::Tensor>> dzs, int64_t lddz, uint64_t acc_mask, int64_t D, bool self,
              int64_t act0) {
   std::vector<const void*> p;
   std::vector<void*> g;
   for (auto& z : zs) p.push_back(z.data_ptr());
   for (auto& d : dzs) g.push_back(mptr(d));
-  TORCH_CHECK(zs.size() >= 1 && zs.size() <= 32 && dzs.size() == zs.size(), "dot interaction backward: 1..32 features");
+  TORCH_CHECK(zs.size() >= 1 && zs.size() <= 64 && dzs.size() == zs.size(), "dot interaction backward: 1..64 features");
+  const long B = dout.size(0);
+  const long F = (long)zs.size();
+  const long np = self ? F * (F + 1) / 2 : F * (F - 1) / 2;
+  const bool wide = F > 32;
   if (dout.scalar_type() == torch::kFloat32) {
-    const long B = dout.size(0);
-    const long F = (long)zs.size();
-    const long np = self ? F * (F + 1) / 2 : F * (F - 1) / 2;
     TORCH_CHECK(D % 2 == 0 && D <= 256, "dot interaction backward fp32: even D <= 256");
-    TORCH_CHECK(dout.numel() >= (B - 1) * ldo + ((D + np + 3) & ~3L) && ldo >= ((D + np + 3) & ~3L),
+    TORCH_CHECK(extent(dout) >= (B - 1) * ldo + ((D + np + 3) & ~3L) && ldo >= ((D + np + 3) & ~3L),
                 "dot interaction backward: dOut row too small");
     for (size_t i = 0; i < zs.size(); ++i) {
-      TORCH_CHECK(zs[i].scalar_type() == torch::kFloat32 && zs[i].numel() >= (B - 1) * ldz + D, "dot bwd: fp32 inputs");
-      if (g[i]) TORCH_CHECK(dzs[i]->scalar_type() == torch::kFloat32 && dzs[i]->numel() >= (B - 1) * lddz + D, "dot bwd: fp32 grads");
+      TORCH_CHECK(zs[i].scalar_type() == torch::kFloat32 && extent(zs[i]) >= (B - 1) * ldz + D, "dot bwd: fp32 inputs");
+      if (g[i]) TORCH_CHECK(dzs[i]->scalar_type() == torch::kFloat32 && extent(*dzs[i]) >= (B - 1) * lddz + D, "dot bwd: fp32 grads");
     }
-    fm_dot_interaction_bwd_f32((const float* const*)p.data(), (int)F, ldz, dout.data_ptr<float>(), ldo, (float* const*)g.data(),
-                               lddz, (unsigned)acc_mask, B, (int)D, self ? 1 : 0, (int)act0, cur());
+    dot_check(wide ? fm_dot_interaction_wide_bwd_f32((const float* const*)p.data(), (int)F, ldz, dout.data_ptr<float>(), ldo,
+                                                     (float* const*)g.data(), lddz, acc_mask, B, (int)D, self ? 1 : 0,
+                                                     (int)act0, cur())
+                   : fm_dot_interaction_bwd_f32((const float* const*)p.data(), (int)F, ldz, dout.data_ptr<float>(), ldo,
+                                                (float* const*)g.data(), lddz, (unsigned)acc_mask, B, (int)D, self ? 1 : 0,
+                                                (int)act0, cur()));
     return;
   }
   TORCH_CHECK(act0 == 10, "dot interaction backward: act0 is fp32-only");
   TORCH_CHECK(D % 8 == 0 && D <= 256, "dot interaction backward: D % 8 == 0, D <= 256");
-  fm_dot_interaction_bwd(p.data(), (int)p.size(), ldz, dout.data_ptr(), ldo, g.data(), lddz, (unsigned)acc_mask,
-                         dout.size(0), (int)D, self ? 1 : 0, cur());
+  if (wide) {   // the wide kernels read whole 16-byte chunks of the dOut row and index rows without a bound
+    TORCH_CHECK(extent(dout) >= (B - 1) * ldo + ((D + np + 7) & ~7L) && ldo >= ((D + np + 7) & ~7L),
+                "dot interaction backward: dOut row too small");
+    for (size_t i = 0; i < zs.size(); ++i) {
+      TORCH_CHECK(zs[i].scalar_type() == torch::kBFloat16 && extent(zs[i]) >= (B - 1) * ldz + D, "dot bwd: bf16 inputs");
+      if (g[i]) TORCH_CHECK(dzs[i]->scalar_type() == torch::kBFloat16 && extent(*dzs[i]) >= (B - 1) * lddz + D, "dot bwd: bf16 grads");
+    }
+    dot_check(fm_dot_interaction_wide_bwd(p.data(), (int)F, ldz, dout.data_ptr(), ldo, g.data(), lddz, acc_mask, B, (int)D,
+                                          self ? 1 : 0, cur()));
+    return;
+  }
+  dot_check(fm_dot_interaction_bwd(p.data(), (int)F, ldz, dout.data_ptr(), ldo, g.data(), lddz, (unsigned)acc_mask, B, (int)D,
+                                   self ? 1 : 0, cur()));
 }
 
 void sgd(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, c10::optional<torch::Tensor> Wc, torch::Tensor lr,
@@ -1482,6 +1514,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("emb_rowwise_adagrad_apply", &emb_rowwise_adagrad_apply);
   m.def("sdp_rowwise_merge", &sdp_rowwise_merge);
   m.def("dot_fwd", &dot_fwd);
+  m.def("dot_block_cap", &dot_block_cap);
   m.def("dot_bwd", &dot_bwd, py::arg("zs"), py::arg("ldz"), py::arg("dout"), py::arg("ldo"), py::arg("dzs"),
         py::arg("lddz"), py::arg("acc_mask"), py::arg("D"), py::arg("self"), py::arg("act0") = 10);
   m.def("sgd", &sgd);

@@ -771,8 +771,12 @@ long dot_block_cap() { return 512L; }
 
 }  // namespace
 
-extern "C" void fm_dot_interaction_fwd_f32(const float* const* z, int F, long ldz, float* out, long ldo, long B, int D,
-                                           int W, int self, hipStream_t s) {
+extern "C" long fm_dot_block_cap() { return dot_block_cap(); }
+
+extern "C" int fm_dot_interaction_fwd_f32(const float* const* z, int F, long ldz, float* out, long ldo, long B, int D,
+                                          int W, int self, hipStream_t s) {
+  if (F < 1) return FM_DOT_FEATURES;
+  if (F > MAXF) return fm_dot_interaction_wide_fwd_f32(z, F, ldz, out, ldo, B, D, W, self, s);
   PtrTabF t;
   for (int i = 0; i < MAXF; ++i) t.p[i] = i < F ? z[i] : nullptr;
   const int waves = 4;
@@ -797,18 +801,21 @@ extern "C" void fm_dot_interaction_fwd_f32(const float* const* z, int F, long ld
       attr = true;
     }
     hipLaunchKernelGGL(ks, dim3((int)blocks), dim3(64 * waves), lds_s, s, t, ldz, out, ldo, B, F, W, self);
-    return;
+    return 0;
   }
   const size_t lds = (size_t)waves * W * 4;
   auto k = !fast ? fm_dot_fwd_f32<0> : D == 128 ? fm_dot_fwd_f32<128> : D == 64 ? fm_dot_fwd_f32<64>
                                      : D == 32 ? fm_dot_fwd_f32<32> : fm_dot_fwd_f32<16>;
   hipLaunchKernelGGL(k, dim3((int)blocks), dim3(64 * waves), lds, s, t, ldz, out, ldo, B, F, D, W, self);
+  return 0;
 }
 
 // act0: activation backward (of z[0]'s producer) applied to dz[0]; ACT_NONE = plain gradient
-extern "C" void fm_dot_interaction_bwd_f32(const float* const* z, int F, long ldz, const float* dout, long ldo,
-                                           float* const* dz, long lddz, unsigned acc_mask, long B, int D, int self,
-                                           int act0, hipStream_t s) {
+extern "C" int fm_dot_interaction_bwd_f32(const float* const* z, int F, long ldz, const float* dout, long ldo,
+                                          float* const* dz, long lddz, unsigned acc_mask, long B, int D, int self,
+                                          int act0, hipStream_t s) {
+  if (F < 1) return FM_DOT_FEATURES;
+  if (F > MAXF) return fm_dot_interaction_wide_bwd_f32(z, F, ldz, dout, ldo, dz, lddz, acc_mask, B, D, self, act0, s);
   PtrTabF t;
   MPtrTabF g;
   for (int i = 0; i < MAXF; ++i) {
@@ -837,7 +844,7 @@ extern "C" void fm_dot_interaction_bwd_f32(const float* const* z, int F, long ld
                       : (acc ? fm_dot_bwd_f32r<1, 16, true> : fm_dot_bwd_f32r<1, 16, false>);
       hipLaunchKernelGGL(k, dim3((int)blocks), dim3(64 * waves), (size_t)waves * wpad * 4, s, t, ldz, dout, ldo, g, lddz,
                          acc_mask, B, F, W, self, act0);
-      return;
+      return 0;
     }
   }
   const int Wr = fast ? ((W + 3) & ~3) : W;        // the vector path stages whole 16-B chunks
@@ -846,10 +853,13 @@ extern "C" void fm_dot_interaction_bwd_f32(const float* const* z, int F, long ld
                                      : D == 32 ? fm_dot_bwd_f32<32> : fm_dot_bwd_f32<16>;
   hipLaunchKernelGGL(k, dim3((int)blocks), dim3(64 * waves), lds, s, t, ldz, dout, ldo, g, lddz, acc_mask, B, F, D, Wr,
                      self, act0);
+  return 0;
 }
 
-extern "C" void fm_dot_interaction_fwd(const void* const* z, int F, long ldz, void* out, long ldo, long B, int D, int W,
-                                       int self, hipStream_t s) {
+extern "C" int fm_dot_interaction_fwd(const void* const* z, int F, long ldz, void* out, long ldo, long B, int D, int W,
+                                      int self, hipStream_t s) {
+  if (F < 1) return FM_DOT_FEATURES;
+  if (F > MAXF) return fm_dot_interaction_wide_fwd(z, F, ldz, out, ldo, B, D, W, self, s);
   PtrTab t;
   for (int i = 0; i < MAXF; ++i) t.p[i] = i < F ? (const unsigned short*)z[i] : nullptr;
   int waves = 4;
@@ -860,14 +870,17 @@ extern "C" void fm_dot_interaction_fwd(const void* const* z, int F, long ldz, vo
     auto k = D == 128 ? fm_dot_fwd_t<128> : D == 64 ? fm_dot_fwd_t<64> : fm_dot_fwd_t<32>;
     hipLaunchKernelGGL(k, dim3((int)blocks), dim3(64 * waves), waves * W * 2, s, t, ldz, (unsigned short*)out, ldo, B,
                        F, W, self);
-    return;
+    return 0;
   }
   hipLaunchKernelGGL(fm_dot_fwd, dim3((int)blocks), dim3(64 * waves), waves * W * 2, s, t, ldz, (unsigned short*)out,
                      ldo, B, F, D, W, self);
+  return 0;
 }
 
-extern "C" void fm_dot_interaction_bwd(const void* const* z, int F, long ldz, const void* dout, long ldo, void* const* dz,
-                                       long lddz, unsigned acc_mask, long B, int D, int self, hipStream_t s) {
+extern "C" int fm_dot_interaction_bwd(const void* const* z, int F, long ldz, const void* dout, long ldo, void* const* dz,
+                                      long lddz, unsigned acc_mask, long B, int D, int self, hipStream_t s) {
+  if (F < 1) return FM_DOT_FEATURES;
+  if (F > MAXF) return fm_dot_interaction_wide_bwd(z, F, ldz, dout, ldo, dz, lddz, acc_mask, B, D, self, s);
   PtrTab t;
   MPtrTab g;
   for (int i = 0; i < MAXF; ++i) {
@@ -885,10 +898,11 @@ extern "C" void fm_dot_interaction_bwd(const void* const* z, int F, long ldz, co
     size_t lds = waves * (32 * D * 2 + W * 2);
     hipLaunchKernelGGL(k, dim3((int)blocks), dim3(64 * waves), lds, s, t, ldz, (const unsigned short*)dout, ldo, g, lddz,
                        acc_mask, B, F, W, self);
-    return;
+    return 0;
   }
   const int Dp = (D + 31) & ~31;
   size_t lds = waves * (32 * Dp * 2 + 32 * 32 * 2);
   hipLaunchKernelGGL(fm_dot_bwd, dim3((int)blocks), dim3(64 * waves), lds, s, t, ldz, (const unsigned short*)dout, ldo,
                      g, lddz, acc_mask, B, F, D, self);
+  return 0;
 }

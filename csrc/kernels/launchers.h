@@ -88,16 +88,31 @@ void fm_sdp_rowwise_merge_segments(int n, int segs, const int* rows, const int* 
                                    int* const* own_count, int* const* slot, int* const* mids, float* const* mg,
                                    int* const* mcount, const int* nmax, const int* mcap, hipStream_t st);
 
-// interaction.hip
-void fm_dot_interaction_fwd_f32(const float* const* z, int F, long ldz, float* out, long ldo, long B, int D, int W,
-                                int self, hipStream_t s);
+// interaction.hip (1..32 features) and interaction_wide.hip (33..64).  Every launcher returns 0, or a
+// status that fm_dot_interaction_error() names and launches nothing: F outside 1..64, or a shape or
+// alignment the wide form (F > 32) does not serve.  The four launchers without "wide" take any
+// F <= 64 and forward to the wide ones past 32 features.
+enum { FM_DOT_FEATURES = 1, FM_DOT_WIDE_D = 2, FM_DOT_WIDE_W = 3, FM_DOT_WIDE_ALIGN = 4 };
+void fm_dot_interaction_error(int status, const char** msg);   // *msg: static text naming the status
+long fm_dot_block_cap();   // blocks (of four waves) of the persistent interaction grids
+int fm_dot_interaction_fwd_f32(const float* const* z, int F, long ldz, float* out, long ldo, long B, int D, int W,
+                               int self, hipStream_t s);
 // act0: activation backward of feature 0's producer applied to dz[0]; 10 = none
-void fm_dot_interaction_bwd_f32(const float* const* z, int F, long ldz, const float* dout, long ldo, float* const* dz,
-                                long lddz, unsigned acc_mask, long B, int D, int self, int act0, hipStream_t s);
-void fm_dot_interaction_fwd(const void* const* z, int F, long ldz, void* out, long ldo, long B, int D, int W, int self,
-                            hipStream_t s);
-void fm_dot_interaction_bwd(const void* const* z, int F, long ldz, const void* dout, long ldo, void* const* dz,
-                            long lddz, unsigned acc_mask, long B, int D, int self, hipStream_t s);
+int fm_dot_interaction_bwd_f32(const float* const* z, int F, long ldz, const float* dout, long ldo, float* const* dz,
+                               long lddz, unsigned acc_mask, long B, int D, int self, int act0, hipStream_t s);
+int fm_dot_interaction_fwd(const void* const* z, int F, long ldz, void* out, long ldo, long B, int D, int W, int self,
+                           hipStream_t s);
+int fm_dot_interaction_bwd(const void* const* z, int F, long ldz, const void* dout, long ldo, void* const* dz,
+                           long lddz, unsigned acc_mask, long B, int D, int self, hipStream_t s);
+int fm_dot_interaction_wide_fwd_f32(const float* const* z, int F, long ldz, float* out, long ldo, long B, int D, int W,
+                                    int self, hipStream_t s);
+int fm_dot_interaction_wide_bwd_f32(const float* const* z, int F, long ldz, const float* dout, long ldo,
+                                    float* const* dz, long lddz, unsigned long long acc_mask, long B, int D, int self,
+                                    int act0, hipStream_t s);
+int fm_dot_interaction_wide_fwd(const void* const* z, int F, long ldz, void* out, long ldo, long B, int D, int W,
+                                int self, hipStream_t s);
+int fm_dot_interaction_wide_bwd(const void* const* z, int F, long ldz, const void* dout, long ldo, void* const* dz,
+                                long lddz, unsigned long long acc_mask, long B, int D, int self, hipStream_t s);
 
 // cross.hip
 void fm_cross_forward(const void* x0, const void* t, const void* x, void* y, long n, int bf16, hipStream_t s);

@@ -383,10 +383,16 @@ class HipEngine : public Engine {
   }
   void add(float* dst, const float* src, int64_t n) override { fm_binary_forward(0, dst, src, dst, n, 0, 0, st_); }
   void dot_fwd(const float* const* z, int F, float* y, int M, int D, int W) override {
-    fm_dot_interaction_fwd_f32(z, F, D, y, W, M, D, W, 0, st_);
+    dot_check(fm_dot_interaction_fwd_f32(z, F, D, y, W, M, D, W, 0, st_));
   }
   void dot_bwd(const float* const* z, int F, const float* dy, float* const* dz, int M, int D, int W, int act0) override {
-    fm_dot_interaction_bwd_f32(z, F, D, dy, W, dz, D, 0u, M, D, 0, act0, st_);
+    dot_check(fm_dot_interaction_bwd_f32(z, F, D, dy, W, dz, D, 0u, M, D, 0, act0, st_));
+  }
+  // a launcher status that is not 0 launched nothing (more than 64 features, or a shape the wide form refuses)
+  static void dot_check(int status) {
+    const char* msg = "";
+    fm_dot_interaction_error(status, &msg);
+    if (status != 0) throw std::runtime_error(std::string("native hip engine: ") + msg);
   }
   void all_to_all(const float* send, const int64_t* send_counts, float* recv, const int64_t* recv_counts) override {
     if (!comm_) {

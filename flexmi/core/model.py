@@ -337,6 +337,10 @@ class FFModel:
         self.loss_op = Loss(self.loss_type)
         self.metrics_op = Metrics(self.loss_type, metrics or [])
         self._refuse_duplicate_inputs()
+        if self.config.device == "gpu":    # shapes the HIP kernels refuse fail here, not at the first step
+            for op in self.layers:
+                if hasattr(op, "check_hip"):
+                    op.check_hip()
         # ---- strategy --------------------------------------------------------
         from flexmi.parallel import strategy as S
         cfg = self.config

@@ -369,7 +369,7 @@ def dot_interaction_backward(inputs, dy, in_grads, accs, self_inter, act0=10):
     """act0 (fp32): the activation backward of input 0's producer applied to its gradient (the
     executor's bottom-MLP fusion: that Linear then takes the gradient as its pre-activation one)."""
     D = inputs[0].shape[-1]
-    mask = 0
+    mask = 0            # one accumulate bit per input, up to bit 63 (an unsigned 64-bit argument)
     for i, a in enumerate(accs):
         if a and in_grads[i] is not None:
             mask |= 1 << i

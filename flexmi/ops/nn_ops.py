@@ -148,11 +148,25 @@ class DotInteraction(Op):
     Inputs: the bottom-MLP output ``x[B,d]`` and F-1 embedding outputs ``e_i[B,d]``.
     Output ``[B, d + F(F-1)/2 (+pad)]`` = concat(x, strictly-lower-triangle of Z·Zᵀ) with
     ``Z[b] = [x; e_1; ...]``, the layout of facebookresearch/dlrm ``interact_features``.
-    On MI355X one wave computes a 32x32 Gram tile per sample with
-    ``v_mfma_f32_32x32x16_bf16`` (F ≤ 32), K = d.
+    On MI355X one wave computes the Gram matrix of a sample with ``v_mfma_f32_32x32x16_bf16``,
+    K = d: one 32x32 tile for F ≤ 32 features (any even d in fp32, d % 16 == 0 in bf16), the
+    three lower tiles of a 2x2 arrangement for 33 ≤ F ≤ 64 (the wide kernels: d % 16 == 0 and
+    d ≤ 256).  More than 64 features run on the CPU backend only; :meth:`check_hip` refuses them
+    at ``compile()`` on a GPU configuration.
     """
     op_type = OperatorType.OP_DOT_INTERACTION
     name_prefix = "DotInteraction"
+    MAX_HIP_FEATURES = 64
+
+    def check_hip(self):
+        """The limits of the HIP kernels (csrc/kernels/interaction*.hip), raised at compile()."""
+        if self.F > self.MAX_HIP_FEATURES:
+            raise ValueError(f"DotInteraction '{self.name}' has {self.F} features: the HIP kernels take at most "
+                             f"{self.MAX_HIP_FEATURES} (1 dense + {self.MAX_HIP_FEATURES - 1} embeddings); "
+                             f"the CPU backend has no limit")
+        if self.F > 32 and (self.d % 16 != 0 or self.d > 256):
+            raise ValueError(f"DotInteraction '{self.name}' has {self.F} features of width {self.d}: with more than "
+                             f"32 features the HIP kernels need a width that is a multiple of 16 and at most 256")
 
     def __init__(self, model, bottom, embs, pad_to=16, self_interaction=False, name=None):
         super().__init__(model, [bottom] + list(embs), name)

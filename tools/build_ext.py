@@ -29,6 +29,8 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 if ARCH != "gfx950":
     ARCH = "gfx950"  # MI355X only
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+# kernel files compiled without the packed-fp32 VALU forms (v_pk_{add,mul,fma}_f32)
+NO_PACKED_FP32 = ("interaction_wide.hip",)
 TORCH_RUNTIME_SRCS = ("step_runner.cc",)   # csrc/runtime sources built into flexmi/_rt (torch + HIP)
 
 
@@ -44,6 +46,14 @@ def _torch_paths():
 def _py_includes():
     import pybind11
     return [sysconfig.get_paths()["include"], pybind11.get_include()]
+
+
+def _kernel_rule(src):
+    o = os.path.join(BUILD, "k_" + os.path.basename(src).replace(".hip", ".o"))
+    rule = [f"build {o}: hipcc {src}"]
+    if os.path.basename(src) in NO_PACKED_FP32:
+        rule.append("  hipflags = $hipflags -Xclang -target-feature -Xclang -packed-fp32-ops")
+    return o, rule
 
 
 def write_ninja(only=None):
@@ -80,8 +90,8 @@ def write_ninja(only=None):
         incs = " ".join(f"-I{p}" for p in tinc)
         objs = []
         for src in sorted(glob.glob(os.path.join(ROOT, "csrc", "kernels", "*.hip"))):
-            o = os.path.join(BUILD, "k_" + os.path.basename(src).replace(".hip", ".o"))
-            lines.append(f"build {o}: hipcc {src}")
+            o, rule = _kernel_rule(src)
+            lines += rule
             objs.append(o)
         b = os.path.join(BUILD, "hip_ops.o")
         bflags = (f"--offload-arch={ARCH} -O2 -std=c++17 -fPIC -D__HIP_PLATFORM_AMD__=1 -DUSE_ROCM=1 "
@@ -167,7 +177,7 @@ def write_ninja(only=None):
                  for src in sorted(glob.glob(os.path.join(ROOT, "csrc", "kernels", "*.hip")))]
         if only == "native":   # kernel objects come from the C target's rules otherwise
             for src in sorted(glob.glob(os.path.join(ROOT, "csrc", "kernels", "*.hip"))):
-                lines.append(f"build {os.path.join(BUILD, 'k_' + os.path.basename(src).replace('.hip', '.o'))}: hipcc {src}")
+                lines += _kernel_rule(src)[1]
         klib = os.path.join(ROOT, "flexmi", "libflexmi_kernels.so")
         lines.append(f"build {klib}: hiplink {' '.join(kobjs)}")
         lines.append(f"  ldflags = -L{ROCM}/lib -Wl,-rpath,{ROCM}/lib -lamdhip64")
