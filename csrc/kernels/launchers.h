@@ -114,6 +114,24 @@ int fm_dot_interaction_wide_fwd(const void* const* z, int F, long ldz, void* out
 int fm_dot_interaction_wide_bwd(const void* const* z, int F, long ldz, const void* dout, long ldo, void* const* dz,
                                 long lddz, unsigned long long acc_mask, long B, int D, int self, hipStream_t s);
 
+// attention.hip: fused multi-head attention on [B, T, heads * dh] operands given as base + row stride
+// (batch stride T * ld); lse is fp32 [B, heads, Tq].  Every launcher returns 0, or a status that
+// fm_attention_error() names and launches nothing.  The backward takes null for an absent gradient;
+// acc_mask bit 0 / 1 / 2: add to dq / dk / dv instead of overwriting.
+enum { FM_ATTN_HEAD_DIM = 1, FM_ATTN_SHAPE = 2, FM_ATTN_ALIGN = 3 };
+void fm_attention_error(int status, const char** msg);   // *msg: static text naming the status
+int fm_attention_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo,
+                     float* lse, int B, int H, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s);
+int fm_attention_fwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o, long ldo,
+                         float* lse, int B, int H, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s);
+int fm_attention_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* o, long ldo,
+                     const void* dout, long lddo, const float* lse, void* dq, long lddq, void* dk, long lddk, void* dv,
+                     long lddv, int acc_mask, int B, int H, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s);
+int fm_attention_bwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* o,
+                         long ldo, const float* dout, long lddo, const float* lse, float* dq, long lddq, float* dk,
+                         long lddk, float* dv, long lddv, int acc_mask, int B, int H, int dh, int Tq, int Tk, int causal,
+                         float scale, hipStream_t s);
+
 // cross.hip
 void fm_cross_forward(const void* x0, const void* t, const void* x, void* y, long n, int bf16, hipStream_t s);
 void fm_cross_backward(const void* dy, const void* x0, const void* t, void* dt, void* dx0, void* dx, long n, int acct,

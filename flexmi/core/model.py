@@ -22,6 +22,7 @@ from flexmi.core.optimizers import AdamOptimizer, Optimizer, SGDOptimizer
 from flexmi.core.tensor import Parameter, Tensor
 from flexmi.core.types import (ActiMode, AggrMode, DataType, LossType, MetricsType, OperatorType,
                                PoolType)
+from flexmi.ops.attention import Attention
 from flexmi.ops.conv import BatchNorm, Conv2D, Pool2D
 from flexmi.ops.cross import CrossCombine
 from flexmi.ops.elementwise import ElementBinary, ElementUnary
@@ -294,6 +295,37 @@ class FFModel:
         v = self.dense(x, rank, ActiMode.AC_MODE_NONE, False, None, vinit, None, pre("v"))
         t = self.dense(v, D, ActiMode.AC_MODE_NONE, True, None, uinit, bias_initializer or ZeroInitializer(), pre("u"))
         return self.cross_combine(x0, t, None if x is x0 else x, name)
+
+    def attention(self, q, k, v, heads, causal=False, scale=None, name=None):
+        """Fused attention core ``softmax(scale q k^T + mask) v`` per head on ``[B, T, heads * dh]``
+        tensors (:class:`flexmi.ops.attention.Attention`); ``scale`` defaults to ``1 / sqrt(dh)``,
+        ``causal`` needs ``Tq == Tk``.  The three inputs must be three tensors."""
+        return self._add(Attention(self, q, k, v, heads, causal, scale, name)).outputs[0]
+
+    def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, bias=True, causal=False,
+                            kernel_initializer=None, name=None):
+        """Multi-head attention on ``query [B, Tq, *]``, ``key`` / ``value [B, Tk, *]``: four ordinary
+        Linear ops ``<name>_q/_k/_v/_o`` (no activation, Glorot-uniform kernels as :meth:`dense`, zero
+        bias) with the fused :meth:`attention` between them; ``kdim`` / ``vdim`` are checked against
+        the inputs' widths when given.  Passing one tensor as query, key and value is
+        self-attention: the projections make three tensors of it.
+
+        Weights map to ``torch.nn.MultiheadAttention(embed_dim, num_heads, batch_first=True)`` with
+        ``E = embed_dim``: ``<name>_q.weight = in_proj_weight[0:E]``, ``<name>_k.weight =
+        in_proj_weight[E:2E]``, ``<name>_v.weight = in_proj_weight[2E:3E]`` (``q_proj_weight`` /
+        ``k_proj_weight`` / ``v_proj_weight`` when kdim or vdim differ from E), the biases the same
+        slices of ``in_proj_bias``, and ``<name>_o`` is ``out_proj``; every kernel is [out, in] on
+        both sides."""
+        for t, d, what in ((key, kdim, "kdim"), (value, vdim, "vdim")):
+            if d and d != t.dims[-1]:
+                raise ValueError(f"multihead_attention: {what} = {d} but the tensor has {t.dims[-1]} features")
+        if embed_dim % num_heads != 0:
+            raise ValueError(f"multihead_attention: embed_dim {embed_dim} is not a multiple of num_heads {num_heads}")
+        pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
+        proj = lambda t, s: self.dense(t, embed_dim, ActiMode.AC_MODE_NONE, bias, None, kernel_initializer, None,  # noqa: E731
+                                       pre(s))
+        q, k, v = proj(query, "q"), proj(key, "k"), proj(value, "v")
+        return proj(self.attention(q, k, v, num_heads, causal, None, name), "o")
 
     def _share(self, op, shared_op):
         """``shared_op`` (``src/runtime/model.cc:157-171``): the new op uses the weights of

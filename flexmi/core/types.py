@@ -129,6 +129,7 @@ class OperatorType(IntEnum):
     OP_EMBEDDING_COLLECTION = 102
     OP_MSELOSS = 103
     OP_CROSS_COMBINE = 104
+    OP_ATTENTION = 105
 
 
 class OpType(IntEnum):

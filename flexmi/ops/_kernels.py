@@ -378,6 +378,21 @@ def dot_interaction_backward(inputs, dy, in_grads, accs, self_inter, act0=10):
                 int(act0))
 
 
+# ------------------------------------------------------------------ fused attention
+def attention_forward(q, k, v, out, lse, heads, causal, scale):
+    """``out = softmax(scale q k^T + causal mask) v`` per head on [B, T, heads * dh] operands (column
+    slices of wider buffers allowed) and the per-row log-sum-exp ``lse`` [B, heads, Tq] fp32
+    (csrc/kernels/attention.hip)."""
+    C().attn_fwd(q, k, v, out, lse, int(heads), bool(causal), float(scale))
+
+
+def attention_backward(q, k, v, out, dout, lse, dq, dk, dv, accs, heads, causal, scale):
+    """The true gradients of :func:`attention_forward`; a ``None`` gradient is not computed, ``accs``
+    are the three accumulate flags."""
+    mask = sum(1 << i for i, (g, a) in enumerate(zip((dq, dk, dv), accs)) if a and g is not None)
+    C().attn_bwd(q, k, v, out, dout, lse, dq, dk, dv, mask, int(heads), bool(causal), float(scale))
+
+
 # ------------------------------------------------------------------ optimizers / loss
 def sgd_update(master, grad, v, compute, lr_tensor, wd, momentum, nesterov, zero_grad=False):
     """zero_grad: the kernel writes the consumed gradient back as zeros (no separate memset)."""

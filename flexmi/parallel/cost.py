@@ -136,6 +136,13 @@ class CostModel:
             byt = sum(_prod(s) for s in list(in_shapes) + list(out_shapes)) * eb
             tc = fl / (peak * 1e12 * self.m.mfma_eff * 0.5) * 1e6
             return L + max(tc, self._bytes_us(byt)), L + 2 * max(tc, self._bytes_us(byt))
+        if t == OperatorType.OP_ATTENTION:
+            # the two products forward, five backward (S and dP recomputed in both backward kernels
+            # count as 2.5x); operands move once, the score matrix never does
+            fl = op.flops(in_shapes, out_shapes)
+            tm = self._bytes_us(sum(_prod(s) for s in list(in_shapes) + list(out_shapes)) * eb)
+            tc = fl / (peak * 1e12 * self.m.mfma_eff) * 1e6
+            return L + max(tc, tm), 2 * L + max(2.5 * tc, 2 * tm)
         # bandwidth-bound ops (elementwise, concat/split, softmax, pool, BN, transpose, ...)
         byt = sum(_prod(s) for s in list(in_shapes) + list(out_shapes)) * eb
         return L + self._bytes_us(byt), L + self._bytes_us(2 * byt)
@@ -153,7 +160,7 @@ class CostModel:
             return 0.25, 0.25
         if t in (OperatorType.OP_CONV2D,):
             return 1.0, 3.0
-        if t == OperatorType.OP_BATCHMATMUL:
+        if t in (OperatorType.OP_BATCHMATMUL, OperatorType.OP_ATTENTION):
             return 1.0, 2.0
         return 1.0, 1.0
 

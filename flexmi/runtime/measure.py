@@ -30,6 +30,8 @@ def _make_clone(op, m, in_shapes, out_shapes):
         m.dot_interaction(ins[0], ins[1:], op.self_interaction)
     elif t == OperatorType.OP_CROSS_COMBINE:
         m.cross_combine(ins[0], ins[1], ins[2] if len(ins) > 2 else None)
+    elif t == OperatorType.OP_ATTENTION:
+        m.attention(ins[0], ins[1], ins[2], op.heads, op.causal, op.scale)
     elif t == OperatorType.OP_CONCAT:
         m.concat(ins, op.axis)
     elif t == OperatorType.OP_BATCHMATMUL:
