@@ -808,6 +808,79 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o
                                 (int)B, (int)heads, (int)(E / heads), (int)Tq, (int)Tk, causal ? 1 : 0, (float)scale, cur()));
 }
 
+// ---- LayerNorm / RMSNorm with fused residual (layernorm.hip) -----------------------------------------
+void ln_check(int refused) {   // the launchers' return value (launchers.h)
+  TORCH_CHECK(refused == 0, refused == 1 ? "layer norm: the HIP kernels take 1 <= D <= 8192"
+                                         : "layer norm backward: workspace smaller than fm_layernorm_ws_bytes(R, D)");
+}
+
+// an [R, D] operand of x's dtype, possibly a column slice of a wider buffer; returns its row stride
+int64_t ln_operand(const char* fn, const torch::Tensor& t, const torch::Tensor& x, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == x.scalar_type() && t.dim() == 2 && t.size(0) == x.size(0) &&
+                  t.size(1) == x.size(1),
+              fn, " ", what, ": [R, D] device tensor of x's dtype and shape expected");
+  const int64_t ld = t.size(0) > 1 ? t.stride(0) : t.size(1);
+  TORCH_CHECK(t.stride(1) == 1 && ld >= t.size(1) && extent(t) >= (t.size(0) - 1) * ld + t.size(1),
+              fn, " ", what, ": unit column stride and a row stride of at least D expected");
+  return ld;
+}
+int64_t ln_operand(const char* fn, const c10::optional<torch::Tensor>& t, const torch::Tensor& x, const char* what) {
+  return given(t) ? ln_operand(fn, *t, x, what) : 0;
+}
+
+// a contiguous fp32 vector of n elements on the device (gamma, beta, their gradients, the statistics)
+void ln_vector(const char* fn, const c10::optional<torch::Tensor>& t, int64_t n, const char* what) {
+  if (!given(t)) return;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->numel() == n,
+              fn, " ", what, ": contiguous fp32 device tensor of ", n, " elements expected");
+}
+
+void ln_first(const char* fn, const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 1 && x.size(1) <= INT32_MAX &&
+                  (x.scalar_type() == torch::kBFloat16 || x.scalar_type() == torch::kFloat32),
+              fn, ": x must be a non-empty [R, D] bf16 or fp32 device tensor");
+}
+
+// y = norm(x + residual) * gamma + beta; stats [R, 2] (mean, rstd), [R] when rms
+void ln_fwd(torch::Tensor x, c10::optional<torch::Tensor> residual, torch::Tensor y, c10::optional<torch::Tensor> gamma,
+            c10::optional<torch::Tensor> beta, torch::Tensor stats, double eps, bool rms) {
+  ln_first("ln_fwd", x);
+  const int64_t R = x.size(0), D = x.size(1);
+  const int64_t ldx = ln_operand("ln_fwd", x, x, "x"), ldr = ln_operand("ln_fwd", residual, x, "residual"),
+                ldy = ln_operand("ln_fwd", y, x, "y");
+  ln_vector("ln_fwd", gamma, D, "gamma");
+  ln_vector("ln_fwd", beta, D, "beta");
+  ln_vector("ln_fwd", stats, rms ? R : 2 * R, "stats");
+  ln_check(fm_layernorm_forward(x.data_ptr(), ldx, cptr(residual), ldr, y.data_ptr(), ldy, fptr(gamma), fptr(beta),
+                                stats.data_ptr<float>(), R, (int)D, (float)eps, rms ? 1 : 0,
+                                is_bf16(x), cur()));
+}
+
+// dx (+)= ds, dresidual (+)= ds (absent: not touched); dgamma += sum_R dy xhat, dbeta += sum_R dy
+void ln_bwd(torch::Tensor x, c10::optional<torch::Tensor> residual, torch::Tensor dy, c10::optional<torch::Tensor> gamma,
+            torch::Tensor stats, c10::optional<torch::Tensor> dx, c10::optional<torch::Tensor> dresidual, bool accx, bool accr,
+            c10::optional<torch::Tensor> dgamma, c10::optional<torch::Tensor> dbeta, c10::optional<torch::Tensor> ws, bool rms) {
+  ln_first("ln_bwd", x);
+  const int64_t R = x.size(0), D = x.size(1);
+  const int64_t ldx = ln_operand("ln_bwd", x, x, "x"), ldr = ln_operand("ln_bwd", residual, x, "residual"),
+                lddy = ln_operand("ln_bwd", dy, x, "dy"), lddx = ln_operand("ln_bwd", dx, x, "dx"),
+                lddr = ln_operand("ln_bwd", dresidual, x, "dresidual");
+  TORCH_CHECK(given(dresidual) ? given(residual) : true, "ln_bwd dresidual: given without a residual");
+  TORCH_CHECK(given(gamma) == given(dgamma) && (!given(dbeta) || given(dgamma)) && (!given(dgamma) || rms || given(dbeta)),
+              "ln_bwd: gamma, dgamma and (LayerNorm) dbeta are given together or not at all");
+  ln_vector("ln_bwd", gamma, D, "gamma");
+  ln_vector("ln_bwd", dgamma, D, "dgamma");
+  ln_vector("ln_bwd", dbeta, D, "dbeta");
+  ln_vector("ln_bwd", stats, rms ? R : 2 * R, "stats");
+  if (given(dgamma))
+    TORCH_CHECK(given(ws) && ws->is_cuda() && ws->scalar_type() == torch::kFloat32 && ws->is_contiguous(),
+                "ln_bwd ws: contiguous fp32 device workspace expected with affine weights");
+  ln_check(fm_layernorm_backward(x.data_ptr(), ldx, cptr(residual), ldr, dy.data_ptr(), lddy, fptr(gamma),
+                                 stats.data_ptr<float>(), mptr(dx), lddx, mptr(dresidual), lddr, accx ? 1 : 0, accr ? 1 : 0,
+                                 fptr(dgamma), rms ? nullptr : fptr(dbeta), fptr(ws), given(ws) ? ws->numel() * 4 : 0, R,
+                                 (int)D, rms ? 1 : 0, is_bf16(x), cur()));
+}
+
 void sgd(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, c10::optional<torch::Tensor> Wc, torch::Tensor lr,
          double wd, double mom, bool nesterov, bool zero_grad) {
   check_update("sgd", W, G, {V}, Wc, lr);
@@ -1598,6 +1671,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("binary_bwd", &binary_bwd);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("ln_fwd", &ln_fwd);
+  m.def("ln_bwd", &ln_bwd);
   m.def("cross_fwd", &cross_fwd);
   m.def("cross_bwd", &cross_bwd);
   m.def("act_bwd_bias", &act_bwd_bias);

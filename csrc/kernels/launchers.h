@@ -132,6 +132,20 @@ int fm_attention_bwd_f32(const float* q, long ldq, const float* k, long ldk, con
                          long lddk, float* dv, long lddv, int acc_mask, int B, int H, int dh, int Tq, int Tk, int causal,
                          float scale, hipStream_t s);
 
+// layernorm.hip: LayerNorm / RMSNorm (rms) over the last dim of [R, D] operands given as base + row
+// stride in elements, s = x + r with r optional.  gamma / beta fp32 [D] or null; stats fp32 [R, 2]
+// (mean, rstd), [R] rstd when rms.  The backward takes null for an absent dx / dr; dgamma / dbeta [D]
+// are added to (dgamma null: no affine weights, ws unused), through a workspace of at least
+// fm_layernorm_ws_bytes(R, D).  Launchers return 0, or having launched nothing 1 (D outside 1..8192) or 2
+// (workspace too small).
+long fm_layernorm_ws_bytes(long R, int D);
+int fm_layernorm_forward(const void* x, long ldx, const void* r, long ldr, void* y, long ldy, const float* gamma,
+                         const float* beta, float* stats, long R, int D, float eps, int rms, int bf16, hipStream_t s);
+int fm_layernorm_backward(const void* x, long ldx, const void* r, long ldr, const void* dy, long lddy,
+                          const float* gamma, const float* stats, void* dx, long lddx, void* dr, long lddr, int accx,
+                          int accr, float* dgamma, float* dbeta, float* ws, long ws_bytes, long R, int D, int rms,
+                          int bf16, hipStream_t s);
+
 // cross.hip
 void fm_cross_forward(const void* x0, const void* t, const void* x, void* y, long n, int bf16, hipStream_t s);
 void fm_cross_backward(const void* dy, const void* x0, const void* t, void* dt, void* dx0, void* dx, long n, int acct,

@@ -28,6 +28,7 @@ from flexmi.ops.cross import CrossCombine
 from flexmi.ops.elementwise import ElementBinary, ElementUnary
 from flexmi.ops.embedding import Embedding
 from flexmi.ops.linear import Linear
+from flexmi.ops.norm import LayerNorm
 from flexmi.ops.nn_ops import BatchMatmul, DotInteraction, Dropout, Softmax
 from flexmi.ops.tensor_ops import Concat, Flat, Reshape, Reverse, Split, Transpose
 from flexmi.parallel.comm import Comm
@@ -326,6 +327,40 @@ class FFModel:
                                        pre(s))
         q, k, v = proj(query, "q"), proj(key, "k"), proj(value, "v")
         return proj(self.attention(q, k, v, num_heads, causal, None, name), "o")
+
+    def layer_norm(self, x, residual=None, eps=1e-5, elementwise_affine=True, rms=False, name=None):
+        """LayerNorm over the last dim of ``x [..., D]`` (:class:`flexmi.ops.norm.LayerNorm`), of ``x +
+        residual`` when a residual of ``x``'s shape is given (the sum is formed in fp32 inside the op).
+        ``rms=True`` is RMSNorm: no mean is subtracted and there is no bias.  Weights ``scale`` = 1 and
+        ``bias`` = 0 unless ``elementwise_affine=False``.  ``residual`` must not be ``x`` itself."""
+        return self._add(LayerNorm(self, x, residual, eps, elementwise_affine, rms, name)).outputs[0]
+
+    def transformer_encoder_layer(self, x, num_heads, dim_feedforward, causal=False, norm_first=False, name=None,
+                                  attention_bias=True):
+        """One transformer encoder layer on ``x [B, T, E]`` without dropout: self-attention
+        (:meth:`multihead_attention`, ``<name>_attn``), a feed-forward of two :meth:`dense` ops
+        ``<name>_ff1`` (ReLU, ``dim_feedforward`` wide) and ``<name>_ff2``, and two :meth:`layer_norm` ops
+        ``<name>_norm1`` / ``<name>_norm2``.  Post-norm (default) uses the fused residual: ``h =
+        layer_norm(attn(x), residual=x)``, ``out = layer_norm(ffn(h), residual=h)``.  ``norm_first``:
+        ``h = x + attn(layer_norm(x))``, ``out = h + ffn(layer_norm(h))`` with the plain :meth:`add`.
+        ``attention_bias=False`` builds the four attention projections without bias.
+
+        Weights map to ``torch.nn.TransformerEncoderLayer(E, num_heads, dim_feedforward, dropout=0,
+        batch_first=True, norm_first=norm_first)``: ``<name>_attn_q/_k/_v/_o`` to ``self_attn`` as
+        :meth:`multihead_attention` documents, ``<name>_ff1`` = ``linear1``, ``<name>_ff2`` = ``linear2``
+        (kernels [out, in] on both sides), ``<name>_norm1/2.scale`` = ``norm1/2.weight`` and ``.bias`` =
+        ``norm1/2.bias``; ``causal`` corresponds to ``src_mask = generate_square_subsequent_mask(T)``."""
+        E = x.dims[-1]
+        pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
+        attn = lambda t: self.multihead_attention(t, t, t, E, num_heads, bias=attention_bias, causal=causal,  # noqa: E731
+                                                  name=pre("attn"))
+        ffn = lambda t: self.dense(self.dense(t, dim_feedforward, ActiMode.AC_MODE_RELU, name=pre("ff1")), E,  # noqa: E731
+                                   name=pre("ff2"))
+        if norm_first:
+            h = self.add(x, attn(self.layer_norm(x, name=pre("norm1"))))
+            return self.add(h, ffn(self.layer_norm(h, name=pre("norm2"))))
+        h = self.layer_norm(attn(x), residual=x, name=pre("norm1"))
+        return self.layer_norm(ffn(h), residual=h, name=pre("norm2"))
 
     def _share(self, op, shared_op):
         """``shared_op`` (``src/runtime/model.cc:157-171``): the new op uses the weights of

@@ -130,6 +130,7 @@ class OperatorType(IntEnum):
     OP_MSELOSS = 103
     OP_CROSS_COMBINE = 104
     OP_ATTENTION = 105
+    OP_LAYERNORM = 106
 
 
 class OpType(IntEnum):

@@ -8,5 +8,6 @@ from .tensor_ops import Concat, Split, Flat, Reshape, Transpose, Reverse  # noqa
 from .nn_ops import Softmax, Dropout, BatchMatmul, DotInteraction  # noqa
 from .cross import CrossCombine  # noqa
 from .attention import Attention  # noqa
+from .norm import LayerNorm  # noqa
 from .conv import Conv2D, Pool2D, BatchNorm  # noqa
 from .rnn import LSTM  # noqa

@@ -393,6 +393,22 @@ def attention_backward(q, k, v, out, dout, lse, dq, dk, dv, accs, heads, causal,
     C().attn_bwd(q, k, v, out, dout, lse, dq, dk, dv, mask, int(heads), bool(causal), float(scale))
 
 
+# ------------------------------------------------------------------ LayerNorm / RMSNorm
+def layernorm_forward(x, residual, y, gamma, beta, stats, eps, rms):
+    """``y = norm(x + residual) * gamma + beta`` over the last dim of [R, D] operands (column slices of
+    wider buffers allowed; ``residual``, ``gamma``, ``beta`` may be None) and the fp32 row statistics
+    ``stats`` [R, 2] (mean, rstd), [R] rstd alone when ``rms`` (csrc/kernels/layernorm.hip)."""
+    C().ln_fwd(x, residual, y, gamma, beta, stats, float(eps), bool(rms))
+
+
+def layernorm_backward(x, residual, dy, gamma, stats, dx, dresidual, accx, accr, dgamma, dbeta, rms):
+    """``dx (+)= ds`` and ``dresidual (+)= ds`` (a None gradient is not touched), ``dgamma += sum_R dy
+    xhat`` and ``dbeta += sum_R dy`` (fp32 [D], both ADDED to; None without affine weights).  Two
+    launches without atomics; the per-block partial sums go through the per-device workspace."""
+    ws = workspace(x.device, GEMM_WS_BYTES) if dgamma is not None else None
+    C().ln_bwd(x, residual, dy, gamma, stats, dx, dresidual, bool(accx), bool(accr), dgamma, dbeta, ws, bool(rms))
+
+
 # ------------------------------------------------------------------ optimizers / loss
 def sgd_update(master, grad, v, compute, lr_tensor, wd, momentum, nesterov, zero_grad=False):
     """zero_grad: the kernel writes the consumed gradient back as zeros (no separate memset)."""

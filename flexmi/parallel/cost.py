@@ -160,7 +160,7 @@ class CostModel:
             return 0.25, 0.25
         if t in (OperatorType.OP_CONV2D,):
             return 1.0, 3.0
-        if t in (OperatorType.OP_BATCHMATMUL, OperatorType.OP_ATTENTION):
+        if t in (OperatorType.OP_BATCHMATMUL, OperatorType.OP_ATTENTION, OperatorType.OP_LAYERNORM):
             return 1.0, 2.0
         return 1.0, 1.0
 
