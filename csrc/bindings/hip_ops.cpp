@@ -881,6 +881,91 @@ void ln_bwd(torch::Tensor x, c10::optional<torch::Tensor> residual, torch::Tenso
                                  (int)D, rms ? 1 : 0, is_bf16(x), cur()));
 }
 
+// ---- MXFP8: block-scaled fp8 quantisers and GEMM (mxfp8.hip) ------------------------------------------
+void mx_check(const char* fn, int refused) {
+  TORCH_CHECK(refused == 0, fn, refused == 1 ? ": operands outside the kernels' contract (widths % 32, 16-B aligned rows)"
+                                             : ": workspace smaller than fm_mx_dact_ws_bytes(R, C)");
+}
+
+// a contiguous uint8 device tensor [rows, cols] (codes or scale bytes)
+void mx_bytes(const char* fn, const c10::optional<torch::Tensor>& t, int64_t rows, int64_t cols, const char* what) {
+  if (!given(t)) return;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kUInt8 && t->is_contiguous() && t->dim() == 2 &&
+                  t->size(0) == rows && t->size(1) == cols,
+              fn, " ", what, ": contiguous uint8 device tensor [", rows, ", ", cols, "] expected");
+}
+
+// an [R, C] bf16 / fp32 operand with unit column stride; returns its row stride
+int64_t mx_operand(const char* fn, const torch::Tensor& t, int64_t R, int64_t C, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.size(0) == R && t.size(1) == C && t.stride(1) == 1 &&
+                  (t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32),
+              fn, " ", what, ": [R, C] bf16 or fp32 device tensor with unit column stride expected");
+  const int64_t ld = R > 1 ? t.stride(0) : C;
+  TORCH_CHECK(ld >= C && extent(t) >= (R - 1) * ld + C, fn, " ", what, ": row stride of at least C expected");
+  return ld;
+}
+
+// the copies' shapes: rc [R, C], rs [R, C/32], cc [C, Rp], cs [C, Rp/32]; returns Rp (0 without cc)
+int64_t mx_copies(const char* fn, int64_t R, int64_t C, const c10::optional<torch::Tensor>& rc,
+                  const c10::optional<torch::Tensor>& rs, const c10::optional<torch::Tensor>& cc,
+                  const c10::optional<torch::Tensor>& cs) {
+  TORCH_CHECK(C % 32 == 0 && given(rc) == given(rs) && given(cc) == given(cs) && (given(rc) || given(cc)), fn,
+              ": C % 32 == 0 and codes given with their scales expected");
+  mx_bytes(fn, rc, R, C, "rc");
+  mx_bytes(fn, rs, R, C / 32, "rs");
+  const int64_t Rp = given(cc) && cc->dim() == 2 ? cc->size(1) : 0;
+  mx_bytes(fn, cc, C, Rp, "cc");
+  mx_bytes(fn, cs, C, Rp / 32, "cs");
+  return Rp;
+}
+
+void mx_quant(torch::Tensor x, int64_t fmt, c10::optional<torch::Tensor> rc, c10::optional<torch::Tensor> rs,
+              c10::optional<torch::Tensor> cc, c10::optional<torch::Tensor> cs) {
+  TORCH_CHECK(x.dim() == 2, "mx_quant x: [R, C] expected");
+  const int64_t R = x.size(0), C = x.size(1), ldx = mx_operand("mx_quant", x, R, C, "x");
+  const int64_t Rp = mx_copies("mx_quant", R, C, rc, rs, cc, cs);
+  mx_check("mx_quant", fm_mx_quant(x.data_ptr(), ldx, is_bf16(x), R, (int)C, (int)fmt, mptr(rc), mptr(rs), mptr(cc),
+                                   mptr(cs), Rp, cur()));
+}
+
+void mx_quant_dact(torch::Tensor dy, torch::Tensor y, int64_t act, torch::Tensor rc, torch::Tensor rs, torch::Tensor cc,
+                   torch::Tensor cs, c10::optional<torch::Tensor> db, c10::optional<torch::Tensor> ws) {
+  TORCH_CHECK(dy.dim() == 2 && y.scalar_type() == dy.scalar_type(), "mx_quant_dact: dy [R, C] and y of one dtype expected");
+  const int64_t R = dy.size(0), C = dy.size(1);
+  const int64_t lddy = mx_operand("mx_quant_dact", dy, R, C, "dy"), ldy = mx_operand("mx_quant_dact", y, R, C, "y");
+  const int64_t Rp = mx_copies("mx_quant_dact", R, C, rc, rs, cc, cs);
+  if (given(db))
+    TORCH_CHECK(db->is_cuda() && db->scalar_type() == torch::kFloat32 && db->is_contiguous() && db->numel() == C &&
+                    given(ws) && ws->is_cuda() && ws->scalar_type() == torch::kFloat32 && ws->is_contiguous(),
+                "mx_quant_dact: db fp32 [C] and a contiguous fp32 workspace expected");
+  mx_check("mx_quant_dact", fm_mx_quant_dact(dy.data_ptr(), lddy, y.data_ptr(), ldy, is_bf16(dy), (int)act, R, (int)C,
+                                             rc.data_ptr(), rs.data_ptr(), cc.data_ptr(), cs.data_ptr(), Rp, fptr(db),
+                                             fptr(ws), given(ws) ? ws->numel() * 4 : 0, cur()));
+}
+
+// C[M, N] (+)= act(A[:M, :K] B[:N, :K]^T + bias): A / B uint8 codes, sa / sb their scale bytes (row strides taken
+// from the tensors, so the padded column-wise copies pass as they are)
+void mx_gemm(torch::Tensor A, torch::Tensor sa, int64_t fmt_a, torch::Tensor B, torch::Tensor sb, int64_t fmt_b,
+             torch::Tensor Cout, c10::optional<torch::Tensor> bias, int64_t act, bool beta, int64_t M, int64_t N, int64_t K) {
+  auto bytes2 = [](const torch::Tensor& t, int64_t rows, int64_t cols, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kUInt8 && t.dim() == 2 && t.size(0) >= rows && t.size(1) >= cols &&
+                    t.stride(1) == 1 && t.stride(0) >= t.size(1) && extent(t) >= (rows - 1) * t.stride(0) + cols,
+                "mx_gemm ", what, ": uint8 device tensor of at least [", rows, ", ", cols, "] with unit column stride expected");
+  };
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 32 && K % 32 == 0 && M <= INT32_MAX && N <= INT32_MAX && K <= INT32_MAX, "mx_gemm: bad sizes");
+  bytes2(A, M, K, "A"); bytes2(sa, M, K / 32, "sa"); bytes2(B, N, K, "B"); bytes2(sb, N, K / 32, "sb");
+  TORCH_CHECK(Cout.is_cuda() && Cout.dim() == 2 && Cout.size(0) == M && Cout.size(1) == N && Cout.stride(1) == 1 &&
+                  (Cout.scalar_type() == torch::kBFloat16 || Cout.scalar_type() == torch::kFloat32) &&
+                  extent(Cout) >= (M - 1) * Cout.stride(0) + N,
+              "mx_gemm C: [M, N] bf16 or fp32 device tensor with unit column stride expected");
+  if (given(bias))
+    TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == torch::kFloat32 && bias->is_contiguous() && bias->numel() == N,
+                "mx_gemm bias: contiguous fp32 [N] expected");
+  mx_check("mx_gemm", fm_mx_gemm(A.data_ptr(), A.stride(0), sa.data_ptr(), sa.stride(0), (int)fmt_a, B.data_ptr(), B.stride(0),
+                                 sb.data_ptr(), sb.stride(0), (int)fmt_b, Cout.data_ptr(), M > 1 ? Cout.stride(0) : N,
+                                 is_bf16(Cout) ? 0 : 1, fptr(bias), (int)act, beta ? 1 : 0, (int)M, (int)N, (int)K, cur()));
+}
+
 void sgd(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, c10::optional<torch::Tensor> Wc, torch::Tensor lr,
          double wd, double mom, bool nesterov, bool zero_grad) {
   check_update("sgd", W, G, {V}, Wc, lr);
@@ -1673,6 +1758,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("ln_fwd", &ln_fwd);
   m.def("ln_bwd", &ln_bwd);
+  m.def("mx_quant", &mx_quant);
+  m.def("mx_quant_dact", &mx_quant_dact);
+  m.def("mx_gemm", &mx_gemm);
   m.def("cross_fwd", &cross_fwd);
   m.def("cross_bwd", &cross_bwd);
   m.def("act_bwd_bias", &act_bwd_bias);

@@ -146,6 +146,24 @@ int fm_layernorm_backward(const void* x, long ldx, const void* r, long ldr, cons
                           int accr, float* dgamma, float* dbeta, float* ws, long ws_bytes, long R, int D, int rms,
                           int bf16, hipStream_t s);
 
+// mxfp8.hip: OCP MX fp8 (fmt 0 = e4m3, 1 = e5m2; one E8M0 scale byte per 32 elements of the contraction
+// dim).  The quantisers read an [R, C] bf16 / fp32 operand (base + row stride in elements, 16-B aligned rows,
+// C % 32 == 0) once and write the row-wise copy (codes rc [R, C], scales rs [R, C/32]) and / or the
+// column-wise one (codes cc [C, Rp], scales cs [C, Rp/32], Rp % 128 == 0, Rp >= R, pad written as zeros);
+// a null pair is not written.  fm_mx_quant_dact quantises dpre = dy * act'(y) (e5m2, both copies) and
+// adds its column sums to db (null: none) through a workspace of at least fm_mx_dact_ws_bytes(R, C).
+// fm_mx_gemm: C[M, N] (+)= act(A[M, K] B[N, K]^T + bias), K % 32 == 0, codes with row strides lda / ldb
+// (multiples of 16), scales with row strides ldsa / ldsb; fmt_b = 0, C bf16 or fp32.  Launchers return
+// 0, or having launched nothing 1 (operands outside this contract) or 2 (workspace too small).
+int fm_mx_quant(const void* x, long ldx, int bf16, long R, int C, int fmt, void* rc, void* rs, void* cc, void* cs,
+                long Rp, hipStream_t s);
+long fm_mx_dact_ws_bytes(long R, int C);
+int fm_mx_quant_dact(const void* dy, long lddy, const void* y, long ldy, int bf16, int act, long R, int C, void* rc,
+                     void* rs, void* cc, void* cs, long Rp, float* db, float* ws, long ws_bytes, hipStream_t s);
+int fm_mx_gemm(const void* A, long lda, const void* sa, long ldsa, int fmt_a, const void* B, long ldb, const void* sb,
+               long ldsb, int fmt_b, void* C, long ldc, int c_fp32, const float* bias, int act, int beta, int M, int N,
+               int K, hipStream_t s);
+
 // cross.hip
 void fm_cross_forward(const void* x0, const void* t, const void* x, void* y, long n, int bf16, hipStream_t s);
 void fm_cross_backward(const void* dy, const void* x0, const void* t, void* dt, void* dx0, void* dx, long n, int acct,

@@ -30,6 +30,7 @@ class FFConfig:
         self.batchSize = 64             # GLOBAL batch size (reference semantics)
         self.printFreq = 0
         self.profiling = False
+        self.linear_fp8 = False         # --linear-fp8: dense() builds MXFP8 layers where the widths allow
         self.debug = False              # serialising executor + NaN guards
         self.learningRate = 0.01
         self.weightDecay = 0.0001
@@ -114,6 +115,8 @@ class FFConfig:
                 self.loadersPerNode = int(nxt())
             elif a == "--profiling":
                 self.profiling = True
+            elif a == "--linear-fp8":
+                self.linear_fp8 = True
             elif a == "--debug":
                 self.debug = True
             elif a == "--overlap":

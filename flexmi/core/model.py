@@ -28,6 +28,7 @@ from flexmi.ops.cross import CrossCombine
 from flexmi.ops.elementwise import ElementBinary, ElementUnary
 from flexmi.ops.embedding import Embedding
 from flexmi.ops.linear import Linear
+from flexmi.ops.linear_mx import LinearMX, mx_eligible
 from flexmi.ops.norm import LayerNorm
 from flexmi.ops.nn_ops import BatchMatmul, DotInteraction, Dropout, Softmax
 from flexmi.ops.tensor_ops import Concat, Flat, Reshape, Reverse, Split, Transpose
@@ -220,7 +221,10 @@ class FFModel:
         return self._add(BatchMatmul(self, A, B, name)).outputs[0]
 
     def dense(self, input, out_dim, activation=ActiMode.AC_MODE_NONE, use_bias=True, shared_op=None,
-              kernel_initializer=None, bias_initializer=None, name=None):
+              kernel_initializer=None, bias_initializer=None, name=None, fp8=None):
+        """``fp8=True`` builds the layer in MXFP8 (:class:`flexmi.ops.linear_mx.LinearMX`; both widths must be
+        multiples of 32, else ValueError), ``False`` an ordinary :class:`Linear`; ``None`` follows
+        ``FFConfig.linear_fp8`` (``--linear-fp8``), under which a layer of other widths quietly stays Linear."""
         if not _is_tensor(input):
             # functional form dense(in_dim, out_dim, act, use_bias, kernel_init, bias_init)
             # (include/model.h:432-436: no shared_op slot -> the 5th/6th args are the initialisers)
@@ -229,9 +233,12 @@ class FFModel:
 
             def chk(t):
                 assert t.dims[-1] == in_dim, f"dense: input has {t.dims[-1]} features, op built for {in_dim}"
-            return DeferredOp(self, lambda t: self.dense(t, out_dim, activation, use_bias, None, ki, bi, name), 1, chk,
+            return DeferredOp(self, lambda t: self.dense(t, out_dim, activation, use_bias, None, ki, bi, name, fp8), 1, chk,
                               "dense")
-        op = Linear(self, input, out_dim, activation, use_bias, kernel_initializer, bias_initializer, name)
+        if fp8 is None:
+            fp8 = getattr(self.config, "linear_fp8", False) and mx_eligible(input.dims[-1], int(out_dim))
+        cls = LinearMX if fp8 else Linear
+        op = cls(self, input, out_dim, activation, use_bias, kernel_initializer, bias_initializer, name)
         self._share(op, shared_op)
         return self._add(op).outputs[0]
 
@@ -304,7 +311,7 @@ class FFModel:
         return self._add(Attention(self, q, k, v, heads, causal, scale, name)).outputs[0]
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, bias=True, causal=False,
-                            kernel_initializer=None, name=None):
+                            kernel_initializer=None, name=None, fp8=None):
         """Multi-head attention on ``query [B, Tq, *]``, ``key`` / ``value [B, Tk, *]``: four ordinary
         Linear ops ``<name>_q/_k/_v/_o`` (no activation, Glorot-uniform kernels as :meth:`dense`, zero
         bias) with the fused :meth:`attention` between them; ``kdim`` / ``vdim`` are checked against
@@ -316,7 +323,7 @@ class FFModel:
         in_proj_weight[E:2E]``, ``<name>_v.weight = in_proj_weight[2E:3E]`` (``q_proj_weight`` /
         ``k_proj_weight`` / ``v_proj_weight`` when kdim or vdim differ from E), the biases the same
         slices of ``in_proj_bias``, and ``<name>_o`` is ``out_proj``; every kernel is [out, in] on
-        both sides."""
+        both sides.  ``fp8`` goes to the four :meth:`dense` calls."""
         for t, d, what in ((key, kdim, "kdim"), (value, vdim, "vdim")):
             if d and d != t.dims[-1]:
                 raise ValueError(f"multihead_attention: {what} = {d} but the tensor has {t.dims[-1]} features")
@@ -324,7 +331,7 @@ class FFModel:
             raise ValueError(f"multihead_attention: embed_dim {embed_dim} is not a multiple of num_heads {num_heads}")
         pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
         proj = lambda t, s: self.dense(t, embed_dim, ActiMode.AC_MODE_NONE, bias, None, kernel_initializer, None,  # noqa: E731
-                                       pre(s))
+                                       pre(s), fp8)
         q, k, v = proj(query, "q"), proj(key, "k"), proj(value, "v")
         return proj(self.attention(q, k, v, num_heads, causal, None, name), "o")
 
@@ -336,14 +343,15 @@ class FFModel:
         return self._add(LayerNorm(self, x, residual, eps, elementwise_affine, rms, name)).outputs[0]
 
     def transformer_encoder_layer(self, x, num_heads, dim_feedforward, causal=False, norm_first=False, name=None,
-                                  attention_bias=True):
+                                  attention_bias=True, fp8=None):
         """One transformer encoder layer on ``x [B, T, E]`` without dropout: self-attention
         (:meth:`multihead_attention`, ``<name>_attn``), a feed-forward of two :meth:`dense` ops
         ``<name>_ff1`` (ReLU, ``dim_feedforward`` wide) and ``<name>_ff2``, and two :meth:`layer_norm` ops
         ``<name>_norm1`` / ``<name>_norm2``.  Post-norm (default) uses the fused residual: ``h =
         layer_norm(attn(x), residual=x)``, ``out = layer_norm(ffn(h), residual=h)``.  ``norm_first``:
         ``h = x + attn(layer_norm(x))``, ``out = h + ffn(layer_norm(h))`` with the plain :meth:`add`.
-        ``attention_bias=False`` builds the four attention projections without bias.
+        ``attention_bias=False`` builds the four attention projections without bias; ``fp8`` goes to all six
+        :meth:`dense` calls.
 
         Weights map to ``torch.nn.TransformerEncoderLayer(E, num_heads, dim_feedforward, dropout=0,
         batch_first=True, norm_first=norm_first)``: ``<name>_attn_q/_k/_v/_o`` to ``self_attn`` as
@@ -353,9 +361,9 @@ class FFModel:
         E = x.dims[-1]
         pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
         attn = lambda t: self.multihead_attention(t, t, t, E, num_heads, bias=attention_bias, causal=causal,  # noqa: E731
-                                                  name=pre("attn"))
-        ffn = lambda t: self.dense(self.dense(t, dim_feedforward, ActiMode.AC_MODE_RELU, name=pre("ff1")), E,  # noqa: E731
-                                   name=pre("ff2"))
+                                                  name=pre("attn"), fp8=fp8)
+        ffn = lambda t: self.dense(self.dense(t, dim_feedforward, ActiMode.AC_MODE_RELU, name=pre("ff1"), fp8=fp8), E,  # noqa: E731
+                                   name=pre("ff2"), fp8=fp8)
         if norm_first:
             h = self.add(x, attn(self.layer_norm(x, name=pre("norm1"))))
             return self.add(h, ffn(self.layer_norm(h, name=pre("norm2"))))

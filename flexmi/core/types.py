@@ -131,6 +131,7 @@ class OperatorType(IntEnum):
     OP_CROSS_COMBINE = 104
     OP_ATTENTION = 105
     OP_LAYERNORM = 106
+    OP_LINEAR_MX = 107
 
 
 class OpType(IntEnum):

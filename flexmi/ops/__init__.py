@@ -9,5 +9,6 @@ from .nn_ops import Softmax, Dropout, BatchMatmul, DotInteraction  # noqa
 from .cross import CrossCombine  # noqa
 from .attention import Attention  # noqa
 from .norm import LayerNorm  # noqa
+from .linear_mx import LinearMX  # noqa
 from .conv import Conv2D, Pool2D, BatchNorm  # noqa
 from .rnn import LSTM  # noqa

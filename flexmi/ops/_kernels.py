@@ -409,6 +409,39 @@ def layernorm_backward(x, residual, dy, gamma, stats, dx, dresidual, accx, accr,
     C().ln_bwd(x, residual, dy, gamma, stats, dx, dresidual, bool(accx), bool(accr), dgamma, dbeta, ws, bool(rms))
 
 
+# ------------------------------------------------------------------ MXFP8 (csrc/kernels/mxfp8.hip)
+def mx_alloc(rows, cols, device, rowwise=True, colwise=True):
+    """uint8 buffers of the MX copies of a [rows, cols] operand: (rc [rows, cols], rs [rows, cols/32], cc
+    [cols, Rp], cs [cols, Rp/32]) with Rp = rows rounded up to 128; a copy not asked for is (None, None)."""
+    from flexmi.ops.mx import pad128
+    u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=device)  # noqa: E731
+    rp = pad128(rows)
+    return ((u8(rows, cols), u8(rows, cols // 32)) if rowwise else (None, None)) + \
+           ((u8(cols, rp), u8(cols, rp // 32)) if colwise else (None, None))
+
+
+def mx_quant(x, fmt, rc, rs, cc, cs):
+    """One read of ``x [R, C]`` (bf16 / fp32, unit column stride) -> its row-wise MX copy (blocks along C) and
+    / or its column-wise one (the transpose, blocks along R, pad rows written as zero codes); ``fmt`` 0 = e4m3,
+    1 = e5m2.  Codes and scale bytes equal :func:`flexmi.ops.mx.mx_quantize_torch` bit for bit."""
+    C().mx_quant(x, int(fmt), rc, rs, cc, cs)
+
+
+def mx_quant_dact(dy, y, act, rc, rs, cc, cs, db):
+    """``dpre = dy * act'(y)`` in fp32 (as ``act_backward_torch``), written as both e5m2 MX copies; ``db +=``
+    its column sums (fp32 [C]; None: not formed) in a fixed order, through the per-device workspace."""
+    need = (dy.shape[0] + 127) // 128 * 4 * dy.shape[1] * 4      # one partial row per 32-row tile
+    ws = workspace(dy.device, max(GEMM_WS_BYTES, need)) if db is not None else None
+    C().mx_quant_dact(dy, y, int(act), rc, rs, cc, cs, db, ws)
+
+
+def mx_gemm(a, sa, fmt_a, b, sb, fmt_b, out, M, N, K, bias=None, act=10, beta=False):
+    """``out[M, N] (+)= act(A[:M, :K] B[:N, :K]^T + bias)`` on the block-scaled fp8 matrix instruction: ``a`` /
+    ``b`` uint8 codes with K contiguous, ``sa`` / ``sb`` their E8M0 bytes; ``out`` bf16 or fp32, ``beta`` adds
+    to it in the one rounding store."""
+    C().mx_gemm(a, sa, int(fmt_a), b, sb, int(fmt_b), out, bias, int(act), bool(beta), int(M), int(N), int(K))
+
+
 # ------------------------------------------------------------------ optimizers / loss
 def sgd_update(master, grad, v, compute, lr_tensor, wd, momentum, nesterov, zero_grad=False):
     """zero_grad: the kernel writes the consumed gradient back as zeros (no separate memset)."""

@@ -37,7 +37,7 @@ def op_signature(op, in_shapes, out_shapes) -> str:
         extra += f"|act={int(op.activation)}"
     if op.op_type == OperatorType.OP_EMBEDDING:
         extra += f"|rows={op.num_entries}"
-    if op.op_type == OperatorType.OP_LINEAR and op.inputs[0].owner_op is None:
+    if op.op_type in (OperatorType.OP_LINEAR, OperatorType.OP_LINEAR_MX) and op.inputs[0].owner_op is None:
         extra += "|nodx"       # first layer: no input gradient GEMM
     return (f"{op.op_type.name}|in={';'.join('x'.join(map(str, s)) for s in in_shapes)}"
             f"|out={';'.join('x'.join(map(str, s)) for s in out_shapes)}{extra}")
@@ -98,7 +98,7 @@ class CostModel:
         peak = self.m.peak_bf16_tflops if eb == 2 else self.m.peak_fp32_tflops
         if getattr(op, "is_view", False) or t in (OperatorType.OP_FLAT, OperatorType.OP_RESHAPE):
             return 0.0, 0.0
-        if t == OperatorType.OP_LINEAR:
+        if t in (OperatorType.OP_LINEAR, OperatorType.OP_LINEAR_MX):   # MX: priced as the bf16 layer, not measured
             K = in_shapes[0][-1]
             N = out_shapes[0][-1]
             M = _prod(out_shapes[0][:-1])
@@ -156,6 +156,8 @@ class CostModel:
             return 0.0, 0.0
         if t == OperatorType.OP_LINEAR:
             return 1.0, 2.0 if op.inputs[0].owner_op is None else 3.0
+        if t == OperatorType.OP_LINEAR_MX:   # two quantisers + GEMM; quantiser, fold and two GEMMs
+            return 3.0, 3.0 if op.inputs[0].owner_op is None else 4.0
         if t == OperatorType.OP_EMBEDDING:
             return 0.25, 0.25
         if t in (OperatorType.OP_CONV2D,):

@@ -48,7 +48,8 @@ def _keys(model):
     out = {}
     for li, op in enumerate(model.layers):
         for wi, w in enumerate(op.weights):
-            out[w.guid] = f"L{li}.{type(op).__name__}.w{wi}"
+            # checkpoint_name: an op whose weights are another op's (LinearMX keys as Linear)
+            out[w.guid] = f"L{li}.{getattr(op, 'checkpoint_name', type(op).__name__)}.w{wi}"
     return out
 
 

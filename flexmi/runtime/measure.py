@@ -24,6 +24,8 @@ def _make_clone(op, m, in_shapes, out_shapes):
     ins = [m.create_tensor(list(s), op.inputs[i].data_type) for i, s in enumerate(in_shapes)]
     if t == OperatorType.OP_LINEAR:
         m.dense(ins[0], out_shapes[0][-1], op.activation, op.use_bias)
+    elif t == OperatorType.OP_LINEAR_MX:
+        m.dense(ins[0], out_shapes[0][-1], op.activation, op.use_bias, fp8=True)
     elif t == OperatorType.OP_EMBEDDING:
         m.embedding(ins[0], op.num_entries, out_shapes[0][-1], op.aggr)
     elif t == OperatorType.OP_DOT_INTERACTION:
@@ -66,7 +68,7 @@ def measure_op(op, in_shapes, out_shapes, reps=20, index_range=None, device="gpu
     cfg.device = device
     cfg.compute_dtype = dtype if device == "gpu" else "fp32"
     # the op's input gradient is part of its backward unless the input is a graph input
-    cfg.input_grads = not (op.op_type == OperatorType.OP_LINEAR and op.inputs[0].owner_op is None)
+    cfg.input_grads = not (op.op_type in (OperatorType.OP_LINEAR, OperatorType.OP_LINEAR_MX) and op.inputs[0].owner_op is None)
     m = FFModel(cfg)
     ins = _make_clone(op, m, in_shapes, out_shapes)
     if ins is None:
