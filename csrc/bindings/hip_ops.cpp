@@ -753,7 +753,7 @@ void attn_check(int status) {
 int64_t attn_operand(const torch::Tensor& t, const torch::Tensor& ref, int64_t T, int64_t E, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == ref.scalar_type() && t.dim() == 3 && t.size(0) == ref.size(0) &&
                   t.size(1) == T && t.size(2) == E,
-              "attention ", what, ": [B, T, heads * dh] device tensor of q's dtype expected");
+              "attention ", what, ": [B, T, heads * dh] ([B, T, kv_heads * dh] for k and v) device tensor of q's dtype expected");
   const int64_t ld = t.stride(1);
   TORCH_CHECK(t.stride(2) == 1 && ld >= E && (t.size(0) == 1 || t.stride(0) == T * ld) &&
                   extent(t) >= (t.size(0) * T - 1) * ld + E,
@@ -766,46 +766,62 @@ void attn_lse_check(const torch::Tensor& lse, int64_t n) {
               "attention lse: contiguous fp32 [B, heads, Tq]");
 }
 
+// null without lengths; else int32, contiguous, one per sample, on the device (read there only)
+const int* attn_lengths(const c10::optional<torch::Tensor>& len, int64_t B) {
+  if (!given(len)) return nullptr;
+  TORCH_CHECK(len->is_cuda() && len->scalar_type() == torch::kInt32 && len->is_contiguous() && len->numel() == B,
+              "attention key_lengths: contiguous int32 device tensor with one length per sample");
+  return len->data_ptr<int>();
+}
+
+// k, v (and dk, dv) are [B, Tk, kv_heads * dh]; key_lengths: see launchers.h
 void attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor out, torch::Tensor lse, int64_t heads,
-              bool causal, double scale) {
+              bool causal, double scale, int64_t kv_heads, c10::optional<torch::Tensor> key_lengths) {
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 || q.scalar_type() == torch::kFloat32, "attention: bf16 or fp32");
   TORCH_CHECK(q.dim() == 3 && heads >= 1 && q.size(2) % heads == 0, "attention: q [B, Tq, heads * dh]");
-  const int64_t B = q.size(0), Tq = q.size(1), E = q.size(2), Tk = k.dim() == 3 ? k.size(1) : 0;
-  const int64_t ldq = attn_operand(q, q, Tq, E, "q"), ldk = attn_operand(k, q, Tk, E, "k"),
-                ldv = attn_operand(v, q, Tk, E, "v"), ldo = attn_operand(out, q, Tq, E, "out");
+  TORCH_CHECK(kv_heads >= 1 && heads % kv_heads == 0, "attention: kv_heads must divide heads");
+  const int64_t B = q.size(0), Tq = q.size(1), E = q.size(2), Tk = k.dim() == 3 ? k.size(1) : 0, Ek = E / heads * kv_heads;
+  const int64_t ldq = attn_operand(q, q, Tq, E, "q"), ldk = attn_operand(k, q, Tk, Ek, "k"),
+                ldv = attn_operand(v, q, Tk, Ek, "v"), ldo = attn_operand(out, q, Tq, E, "out");
   attn_lse_check(lse, B * heads * Tq);
+  const int* len = attn_lengths(key_lengths, B);
   if (q.scalar_type() == torch::kFloat32)
     attn_check(fm_attention_fwd_f32(q.data_ptr<float>(), ldq, k.data_ptr<float>(), ldk, v.data_ptr<float>(), ldv,
-                                    out.data_ptr<float>(), ldo, lse.data_ptr<float>(), (int)B, (int)heads, (int)(E / heads),
-                                    (int)Tq, (int)Tk, causal ? 1 : 0, (float)scale, cur()));
+                                    out.data_ptr<float>(), ldo, lse.data_ptr<float>(), (int)B, (int)heads, (int)kv_heads,
+                                    (int)(E / heads), (int)Tq, (int)Tk, len, causal ? 1 : 0, (float)scale, cur()));
   else
     attn_check(fm_attention_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo,
-                                lse.data_ptr<float>(), (int)B, (int)heads, (int)(E / heads), (int)Tq, (int)Tk, causal ? 1 : 0,
-                                (float)scale, cur()));
+                                lse.data_ptr<float>(), (int)B, (int)heads, (int)kv_heads, (int)(E / heads), (int)Tq, (int)Tk,
+                                len, causal ? 1 : 0, (float)scale, cur()));
 }
 
 // acc_mask bit 0 / 1 / 2: dq / dk / dv are added to; an absent gradient is not computed
 void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor out, torch::Tensor dout, torch::Tensor lse,
               c10::optional<torch::Tensor> dq, c10::optional<torch::Tensor> dk, c10::optional<torch::Tensor> dv,
-              int64_t acc_mask, int64_t heads, bool causal, double scale) {
+              int64_t acc_mask, int64_t heads, bool causal, double scale, int64_t kv_heads,
+              c10::optional<torch::Tensor> key_lengths) {
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 || q.scalar_type() == torch::kFloat32, "attention: bf16 or fp32");
   TORCH_CHECK(q.dim() == 3 && heads >= 1 && q.size(2) % heads == 0, "attention: q [B, Tq, heads * dh]");
-  const int64_t B = q.size(0), Tq = q.size(1), E = q.size(2), Tk = k.dim() == 3 ? k.size(1) : 0;
-  const int64_t ldq = attn_operand(q, q, Tq, E, "q"), ldk = attn_operand(k, q, Tk, E, "k"),
-                ldv = attn_operand(v, q, Tk, E, "v"), ldo = attn_operand(out, q, Tq, E, "out"),
+  TORCH_CHECK(kv_heads >= 1 && heads % kv_heads == 0, "attention: kv_heads must divide heads");
+  const int64_t B = q.size(0), Tq = q.size(1), E = q.size(2), Tk = k.dim() == 3 ? k.size(1) : 0, Ek = E / heads * kv_heads;
+  const int64_t ldq = attn_operand(q, q, Tq, E, "q"), ldk = attn_operand(k, q, Tk, Ek, "k"),
+                ldv = attn_operand(v, q, Tk, Ek, "v"), ldo = attn_operand(out, q, Tq, E, "out"),
                 lddo = attn_operand(dout, q, Tq, E, "dout");
-  const int64_t lddq = given(dq) ? attn_operand(*dq, q, Tq, E, "dq") : 0, lddk = given(dk) ? attn_operand(*dk, q, Tk, E, "dk") : 0,
-                lddv = given(dv) ? attn_operand(*dv, q, Tk, E, "dv") : 0;
+  const int64_t lddq = given(dq) ? attn_operand(*dq, q, Tq, E, "dq") : 0, lddk = given(dk) ? attn_operand(*dk, q, Tk, Ek, "dk") : 0,
+                lddv = given(dv) ? attn_operand(*dv, q, Tk, Ek, "dv") : 0;
   attn_lse_check(lse, B * heads * Tq);
+  const int* len = attn_lengths(key_lengths, B);
   if (q.scalar_type() == torch::kFloat32)
     attn_check(fm_attention_bwd_f32(q.data_ptr<float>(), ldq, k.data_ptr<float>(), ldk, v.data_ptr<float>(), ldv,
                                     out.data_ptr<float>(), ldo, dout.data_ptr<float>(), lddo, lse.data_ptr<float>(),
                                     (float*)mptr(dq), lddq, (float*)mptr(dk), lddk, (float*)mptr(dv), lddv, (int)acc_mask,
-                                    (int)B, (int)heads, (int)(E / heads), (int)Tq, (int)Tk, causal ? 1 : 0, (float)scale, cur()));
+                                    (int)B, (int)heads, (int)kv_heads, (int)(E / heads), (int)Tq, (int)Tk, len, causal ? 1 : 0,
+                                    (float)scale, cur()));
   else
     attn_check(fm_attention_bwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, dout.data_ptr(),
                                 lddo, lse.data_ptr<float>(), mptr(dq), lddq, mptr(dk), lddk, mptr(dv), lddv, (int)acc_mask,
-                                (int)B, (int)heads, (int)(E / heads), (int)Tq, (int)Tk, causal ? 1 : 0, (float)scale, cur()));
+                                (int)B, (int)heads, (int)kv_heads, (int)(E / heads), (int)Tq, (int)Tk, len, causal ? 1 : 0,
+                                (float)scale, cur()));
 }
 
 // ---- LayerNorm / RMSNorm with fused residual (layernorm.hip) -----------------------------------------

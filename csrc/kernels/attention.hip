@@ -15,7 +15,7 @@
 //   So K and V tiles lie in LDS row-major exactly as in memory, staged with 16-byte accesses; the
 //   next tile's global loads are issued into registers before the current tile's MFMAs and written
 //   to LDS after them (35 KB of LDS per block at DH = 128: two blocks fit a CU with room to spare).
-// Forward: grid (ceil(Tq / 128), heads, B), 4 waves of 32 queries; key tiles of 64 (bf16) or 32
+// Forward: grid (ceil(Tq GS / 128), heads / GS, B), 4 waves of 32 queries; key tiles of 64 (bf16) or 32
 //   (fp32) rows.  Online softmax in the exp2 domain (scale * log2 e folded into one multiply), the
 //   O accumulators are rescaled only when some lane's running maximum moved, key tiles wholly above
 //   the causal diagonal are skipped, tails and the diagonal are masked in the tile (-inf scores).
@@ -23,13 +23,29 @@
 // Backward, two kernels, no atomics, nothing summed across blocks (deterministic):
 //   dQ kernel, the forward's skeleton: P^T from lse, dP^T = V dO^T, dS^T = P^T (dP^T - delta) scale,
 //     dQ^T += K^T dS^T; delta = rowsum(dO * O) from the wave's own register fragments.
-//   dK/dV kernel, grid (ceil(Tk / 128), heads, B), a wave holds 32 keys' K and V rows in registers and
+//   dK/dV kernel, grid (ceil(Tk / 128), KV heads, B), a wave holds 32 keys' K and V rows in registers and
 //     loops over staged query tiles (Q, dO, lse, and delta recomputed while dO and O are staged):
 //     S = Q K^T, dP = dO V^T (a lane owns one key), dV^T += dO^T P, dK^T += Q^T dS.
 //   The accumulate flag is applied in the final store (load, add in fp32, round once).
 // fp32 storage runs the same kernels on v_mfma_f32_32x32x2_f32 with P and dS kept in fp32; its
 // k-slices are the two halves of a row (lane half h holds columns h DH/2 ..), so fragments load as
 // float4.  bf16 rounds P and dS to bf16 for the second product, the sums l stay fp32.
+// Key lengths (klens, int32 [B], read on the device only; null: every key): key j of sample b takes part
+//   iff j < klen = clamp(klens[b], 0, Tk).  klen replaces Tk wherever keys are bounded: the tile count (tiles
+//   wholly past klen are never staged), the masks, and the rows a tile stages (padded rows are zeros in
+//   LDS, their contents never meet an MFMA).  Query rows are never masked.  klen == 0 is the only way a
+//   row can see no key: the forward stores output 0 and lse 0 for it, both backward kernels then visit no
+//   key of that sample, so the row adds nothing to any gradient.  Padded key rows get dk = dv = 0 (left
+//   alone under accumulate); a dK/dV lane of a padded key holds the fragments of the last visible key
+//   instead of its own, so that its (select-zeroed) P and dS columns only ever multiply finite values.
+// Grouped-query heads: k/v/dk/dv are [B, Tk, KH * DH], query head hd reads KV head hd / G, G = H / KH.
+//   dK/dV: grid.y is the KV head, the block stages Q, dO, O and lse of the group's G query heads one
+//   after the other inside the query-tile loop and sums them in one pair of register accumulators, in a
+//   fixed order.  Forward and dQ: GS in {1, 2, 4} query heads of one group share a block (GS divides G):
+//   wave w serves head GS blockIdx.y + w % GS and 32 of the block's 128 / GS query rows, so one staged
+//   K/V tile feeds GS heads and K/V traffic falls GS-fold.  GS = 1 is the one-head block of plain MHA.
+// Both are a template switch (EXT): without lengths and with G = 1 the dense instantiations run, which
+//   hold none of this code.
 // Supported: DH in {32, 64, 128}, any Tq, Tk >= 1, 16-byte aligned bases and row strides.
 #include "common.h"
 
@@ -212,22 +228,28 @@ template <typename T, int DH> FM_DEVICE void store_rows(const f32x16_t (&acc)[DH
 
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
+// the keys of sample b that take part (block-uniform)
+FM_DEVICE int key_count(const int* __restrict__ klens, int b, int Tk) { return klens ? min(max(klens[b], 0), Tk) : Tk; }
+
 // ---- forward ---------------------------------------------------------------------------------------
-template <typename T, int DH>
+template <typename T, int DH, int GS, bool EXT>
 __global__ void __launch_bounds__(256) fm_attn_fwd(const T* __restrict__ q, long ldq, const T* __restrict__ k, long ldk,
                                                    const T* __restrict__ v, long ldv, T* __restrict__ o, long ldo,
-                                                   float* __restrict__ lse, int H, int Tq, int Tk, int causal, float sc2) {
+                                                   float* __restrict__ lse, const int* __restrict__ klens, int H, int G,
+                                                   int Tq, int Tk, int causal, float sc2) {
   constexpr int KT = Cfg<T>::KT, LD = DH + Cfg<T>::PAD, NT = DH / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* ks = reinterpret_cast<T*>(smem);
   T* vs = ks + KT * LD;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int hd = blockIdx.y, b = blockIdx.z;
+  constexpr int QB = 128 / GS;                                   // query rows of a block
+  const int hd = blockIdx.y * GS + wave % GS, kvh = EXT ? blockIdx.y * GS / G : hd, b = blockIdx.z;
+  const int klen = EXT ? key_count(klens, b, Tk) : Tk;
   q += (long)b * Tq * ldq + hd * DH;
-  k += (long)b * Tk * ldk + hd * DH;
-  v += (long)b * Tk * ldv + hd * DH;
+  k += (long)b * Tk * ldk + kvh * DH;
+  v += (long)b * Tk * ldv + kvh * DH;
   o += (long)b * Tq * ldo + hd * DH;
-  const int q0 = blockIdx.x * 128 + wave * 32, qi = q0 + r;
+  const int q0 = blockIdx.x * QB + wave / GS * 32, qi = q0 + r;
   const bool active = q0 < Tq;                                   // wave-uniform
   Frag<T, DH> qf;
   load_frag(qf, q + (long)min(qi, Tq - 1) * ldq, h);
@@ -237,24 +259,24 @@ __global__ void __launch_bounds__(256) fm_attn_fwd(const T* __restrict__ q, long
 #pragma unroll
     for (int t = 0; t < 16; ++t) acc[nt][t] = 0.f;
   float m = -INFINITY, l = 0.f;                                  // l: this lane's keys only until the epilogue
-  int nkt = (Tk + KT - 1) / KT;
-  if (causal) nkt = min(nkt, min(blockIdx.x * 128 + 127, Tq - 1) / KT + 1);
+  int nkt = (klen + KT - 1) / KT;
+  if (causal) nkt = min(nkt, min(blockIdx.x * QB + QB - 1, Tq - 1) / KT + 1);
   Stage<T, DH, KT> sk, sv;
-  sk.load(k, ldk, 0, Tk, tid);
-  sv.load(v, ldv, 0, Tk, tid);
+  sk.load(k, ldk, 0, klen, tid);
+  sv.load(v, ldv, 0, klen, tid);
   for (int kt = 0; kt < nkt; ++kt) {
     __syncthreads();                                             // the previous tile has been read
     sk.store(ks, tid);
     sv.store(vs, tid);
     __syncthreads();
     if (kt + 1 < nkt) {
-      sk.load(k, ldk, (kt + 1) * KT, Tk, tid);
-      sv.load(v, ldv, (kt + 1) * KT, Tk, tid);
+      sk.load(k, ldk, (kt + 1) * KT, klen, tid);
+      sv.load(v, ldv, (kt + 1) * KT, klen, tid);
     }
     const int k0 = kt * KT;
     if (!active || (causal && k0 > q0 + 31)) continue;           // wave-uniform
     f32x16_t s[KT / 32];
-    const bool mask = k0 + KT > Tk || (causal && k0 + KT - 1 > q0);
+    const bool mask = k0 + KT > klen || (causal && k0 + KT - 1 > q0);
     float mx = -INFINITY;
 #pragma unroll
     for (int t = 0; t < KT / 32; ++t) {
@@ -266,14 +288,14 @@ __global__ void __launch_bounds__(256) fm_attn_fwd(const T* __restrict__ q, long
         float x = s[t][e] * sc2;
         if (mask) {
           const int key = k0 + 32 * t + acc_row(e, h);
-          if (key >= Tk || (causal && key > qi)) x = -INFINITY;
+          if (key >= klen || (causal && key > qi)) x = -INFINITY;
         }
         s[t][e] = x;
         mx = fmaxf(mx, x);
       }
     }
     mx = fmaxf(mx, other_half(mx));
-    const float mn = fmaxf(m, mx);                               // finite: key 0 is visible to every row
+    const float mn = fmaxf(m, mx);                               // finite: a tile is visited only if klen >= 1: key 0 is visible
     const float alpha = __builtin_amdgcn_exp2f(m - mn);
     if (__builtin_amdgcn_ballot_w64(mn > m) != 0) {
 #pragma unroll
@@ -297,32 +319,36 @@ __global__ void __launch_bounds__(256) fm_attn_fwd(const T* __restrict__ q, long
   if (!active) return;
   l += other_half(l);
   if (qi < Tq) {
-    store_rows<T, DH>(acc, o + (long)qi * ldo, 1.f / l, false, h);
-    if (h == 0) lse[((long)b * H + hd) * Tq + qi] = m * LN2 + __logf(l);
+    // no visible key (klen == 0): output 0, and an lse the backward never uses (it visits no key either)
+    const bool empty = EXT && l <= 0.f;
+    store_rows<T, DH>(acc, o + (long)qi * ldo, empty ? 0.f : 1.f / l, false, h);
+    if (h == 0) lse[((long)b * H + hd) * Tq + qi] = empty ? 0.f : m * LN2 + __logf(l);
   }
 }
 
 // ---- backward: dQ ------------------------------------------------------------------------------------
-template <typename T, int DH>
+template <typename T, int DH, int GS, bool EXT>
 __global__ void __launch_bounds__(256) fm_attn_dq(const T* __restrict__ q, long ldq, const T* __restrict__ k, long ldk,
                                                   const T* __restrict__ v, long ldv, const T* __restrict__ o, long ldo,
                                                   const T* __restrict__ dout, long lddo, const float* __restrict__ lse,
-                                                  T* __restrict__ dq, long lddq, int add, int H, int Tq, int Tk,
-                                                  int causal, float scale) {
+                                                  T* __restrict__ dq, long lddq, int add, const int* __restrict__ klens,
+                                                  int H, int G, int Tq, int Tk, int causal, float scale) {
   constexpr int KT = Cfg<T>::KT, LD = DH + Cfg<T>::PAD, NT = DH / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* ks = reinterpret_cast<T*>(smem);
   T* vs = ks + KT * LD;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int hd = blockIdx.y, b = blockIdx.z;
+  constexpr int QB = 128 / GS;                                   // query rows of a block
+  const int hd = blockIdx.y * GS + wave % GS, kvh = EXT ? blockIdx.y * GS / G : hd, b = blockIdx.z;
+  const int klen = EXT ? key_count(klens, b, Tk) : Tk;
   const float sc2 = scale * LOG2E;
   q += (long)b * Tq * ldq + hd * DH;
-  k += (long)b * Tk * ldk + hd * DH;
-  v += (long)b * Tk * ldv + hd * DH;
+  k += (long)b * Tk * ldk + kvh * DH;
+  v += (long)b * Tk * ldv + kvh * DH;
   o += (long)b * Tq * ldo + hd * DH;
   dout += (long)b * Tq * lddo + hd * DH;
   dq += (long)b * Tq * lddq + hd * DH;
-  const int q0 = blockIdx.x * 128 + wave * 32, qi = q0 + r, qc = min(qi, Tq - 1);
+  const int q0 = blockIdx.x * QB + wave / GS * 32, qi = q0 + r, qc = min(qi, Tq - 1);
   const bool active = q0 < Tq;
   Frag<T, DH> qf, dof;
   load_frag(qf, q + (long)qc * ldq, h);
@@ -340,19 +366,19 @@ __global__ void __launch_bounds__(256) fm_attn_dq(const T* __restrict__ q, long 
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
     for (int t = 0; t < 16; ++t) acc[nt][t] = 0.f;
-  int nkt = (Tk + KT - 1) / KT;
-  if (causal) nkt = min(nkt, min(blockIdx.x * 128 + 127, Tq - 1) / KT + 1);
+  int nkt = (klen + KT - 1) / KT;
+  if (causal) nkt = min(nkt, min(blockIdx.x * QB + QB - 1, Tq - 1) / KT + 1);
   Stage<T, DH, KT> sk, sv;
-  sk.load(k, ldk, 0, Tk, tid);
-  sv.load(v, ldv, 0, Tk, tid);
+  sk.load(k, ldk, 0, klen, tid);
+  sv.load(v, ldv, 0, klen, tid);
   for (int kt = 0; kt < nkt; ++kt) {
     __syncthreads();
     sk.store(ks, tid);
     sv.store(vs, tid);
     __syncthreads();
     if (kt + 1 < nkt) {
-      sk.load(k, ldk, (kt + 1) * KT, Tk, tid);
-      sv.load(v, ldv, (kt + 1) * KT, Tk, tid);
+      sk.load(k, ldk, (kt + 1) * KT, klen, tid);
+      sv.load(v, ldv, (kt + 1) * KT, klen, tid);
     }
     const int k0 = kt * KT;
     if (!active || (causal && k0 > q0 + 31)) continue;
@@ -366,7 +392,7 @@ __global__ void __launch_bounds__(256) fm_attn_dq(const T* __restrict__ q, long 
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int key = k0 + 32 * t + acc_row(e, h);
-        const float p = (key >= Tk || (causal && key > qi)) ? 0.f : __builtin_amdgcn_exp2f(s[e] * sc2 - lse2);
+        const float p = (key >= klen || (causal && key > qi)) ? 0.f : __builtin_amdgcn_exp2f(s[e] * sc2 - lse2);
         s[e] = p * (dp[e] - delta) * scale;
       }
       mma_acc<DH>(acc, ks + 32 * t * LD, s, lane);
@@ -376,12 +402,13 @@ __global__ void __launch_bounds__(256) fm_attn_dq(const T* __restrict__ q, long 
 }
 
 // ---- backward: dK and dV -------------------------------------------------------------------------------
-template <typename T, int DH>
+template <typename T, int DH, bool EXT>
 __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long ldq, const T* __restrict__ k, long ldk,
                                                    const T* __restrict__ v, long ldv, const T* __restrict__ o, long ldo,
                                                    const T* __restrict__ dout, long lddo, const float* __restrict__ lse,
                                                    T* __restrict__ dk, long lddk, T* __restrict__ dv, long lddv, int addk,
-                                                   int addv, int H, int Tq, int Tk, int causal, float scale) {
+                                                   int addv, const int* __restrict__ klens, int H, int Gq, int Tq, int Tk,
+                                                   int causal, float scale) {
   constexpr int QT = Cfg<T>::KT, LD = DH + Cfg<T>::PAD, NT = DH / 32;
   typedef Stage<T, DH, QT> St;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -390,31 +417,38 @@ __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long
   float* lses = reinterpret_cast<float*>(dos + QT * LD);
   float* dels = lses + QT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  const int hd = blockIdx.y, b = blockIdx.z;
+  const int kvh = blockIdx.y, b = blockIdx.z;                    // the group's query heads: kvh G .. kvh G + G - 1
+  const int G = EXT ? Gq : 1, klen = EXT ? key_count(klens, b, Tk) : Tk;
+  // consecutive blocks go to different dies of the chip whatever their cost: with lengths the key blocks of a
+  // (sample, head) are rotated by sample + head, so that no die gets the low, mostly live, key blocks only
+  const int kb = EXT ? (blockIdx.x + kvh + b) % gridDim.x : blockIdx.x;
   const float sc2 = scale * LOG2E;
-  q += (long)b * Tq * ldq + hd * DH;
-  k += (long)b * Tk * ldk + hd * DH;
-  v += (long)b * Tk * ldv + hd * DH;
-  o += (long)b * Tq * ldo + hd * DH;
-  dout += (long)b * Tq * lddo + hd * DH;
-  lse += ((long)b * H + hd) * Tq;
-  const int key0 = blockIdx.x * 128 + wave * 32, kj = key0 + r;
-  const bool active = key0 < Tk;
+  q += (long)b * Tq * ldq + kvh * G * DH;
+  k += (long)b * Tk * ldk + kvh * DH;
+  v += (long)b * Tk * ldv + kvh * DH;
+  o += (long)b * Tq * ldo + kvh * G * DH;
+  dout += (long)b * Tq * lddo + kvh * G * DH;
+  lse += ((long)b * H + kvh * G) * Tq;
+  const int key0 = kb * 128 + wave * 32, kj = key0 + r;
+  const bool active = key0 < klen;
+  // a lane past klen takes the last visible key's rows: finite operands under its zeroed P and dS columns
+  const int kc = EXT ? max(min(kj, klen - 1), 0) : min(kj, Tk - 1);
   Frag<T, DH> kf, vf;
-  load_frag(kf, k + (long)min(kj, Tk - 1) * ldk, h);
-  load_frag(vf, v + (long)min(kj, Tk - 1) * ldv, h);
+  load_frag(kf, k + (long)kc * ldk, h);
+  load_frag(vf, v + (long)kc * ldv, h);
   f32x16_t acck[NT], accv[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
     for (int t = 0; t < 16; ++t) acck[nt][t] = accv[nt][t] = 0.f;
-  const int nqt = (Tq + QT - 1) / QT;
-  for (int qt = causal ? blockIdx.x * 128 / QT : 0; qt < nqt; ++qt) {
+  const int nqt = EXT && kb * 128 >= klen ? 0 : (Tq + QT - 1) / QT;   // a block wholly past klen stages nothing
+  const int qt0 = causal ? kb * 128 / QT : 0;
+  for (int qt = qt0, gi = 0; qt < nqt; ++gi == G ? (gi = 0, ++qt) : 0) {   // per query tile the group's heads in order
     const int qb = qt * QT;
     St sq, sd, so;
-    sq.load(q, ldq, qb, Tq, tid);
-    sd.load(dout, lddo, qb, Tq, tid);
-    so.load(o, ldo, qb, Tq, tid);
+    sq.load(q + gi * DH, ldq, qb, Tq, tid);
+    sd.load(dout + gi * DH, lddo, qb, Tq, tid);
+    so.load(o + gi * DH, ldo, qb, Tq, tid);
     __syncthreads();                                             // the previous tile has been read
     sq.store(qs, tid);
     sd.store(dos, tid);
@@ -427,7 +461,7 @@ __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long
       const int c = tid + 256 * t;
       if (c % St::CPR == 0) dels[c / St::CPR] = d;
     }
-    if (tid < QT) lses[tid] = qb + tid < Tq ? lse[qb + tid] * LOG2E : 0.f;
+    if (tid < QT) lses[tid] = qb + tid < Tq ? (EXT ? lse + (long)gi * Tq : lse)[qb + tid] * LOG2E : 0.f;
     __syncthreads();
     if (!active || (causal && qb + QT - 1 < key0)) continue;     // wave-uniform
 #pragma unroll
@@ -440,7 +474,7 @@ __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int i = 32 * t + acc_row(e, h), qi = qb + i;
-        const float p = (qi >= Tq || kj >= Tk || (causal && kj > qi)) ? 0.f : __builtin_amdgcn_exp2f(s[e] * sc2 - lses[i]);
+        const float p = (qi >= Tq || kj >= klen || (causal && kj > qi)) ? 0.f : __builtin_amdgcn_exp2f(s[e] * sc2 - lses[i]);
         s[e] = p;
         dp[e] = p * (dp[e] - dels[i]) * scale;
       }
@@ -448,56 +482,100 @@ __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long
       mma_acc<DH>(acck, qs + 32 * t * LD, dp, lane);
     }
   }
-  if (!active || kj >= Tk) return;
-  if (dk != nullptr) store_rows<T, DH>(acck, dk + ((long)b * Tk + kj) * lddk + hd * DH, 1.f, addk != 0, h);
-  if (dv != nullptr) store_rows<T, DH>(accv, dv + ((long)b * Tk + kj) * lddv + hd * DH, 1.f, addv != 0, h);
+  if (kj >= Tk || (!EXT && !active)) return;
+  if (EXT && kj >= klen) {                                              // a padded key: zeros, or the old value under accumulate
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int t = 0; t < 16; ++t) acck[nt][t] = accv[nt][t] = 0.f;
+    if (addk) dk = nullptr;
+    if (addv) dv = nullptr;
+  }
+  if (dk != nullptr) store_rows<T, DH>(acck, dk + ((long)b * Tk + kj) * lddk + kvh * DH, 1.f, addk != 0, h);
+  if (dv != nullptr) store_rows<T, DH>(accv, dv + ((long)b * Tk + kj) * lddv + kvh * DH, 1.f, addv != 0, h);
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-template <typename T> int attn_status(int B, int H, int dh, int Tq, int Tk, int causal, std::initializer_list<const void*> ptrs,
-                                      std::initializer_list<long> lds) {
+// qlds: row strides of the [*, H dh] operands, kvlds: of the [*, KH dh] ones
+template <typename T> int attn_status(int B, int H, int KH, int dh, int Tq, int Tk, int causal,
+                                      std::initializer_list<const void*> ptrs, std::initializer_list<long> qlds,
+                                      std::initializer_list<long> kvlds) {
   if (dh != 32 && dh != 64 && dh != 128) return FM_ATTN_HEAD_DIM;
   if (B < 1 || H < 1 || Tq < 1 || Tk < 1 || B > 65535 || H > 65535 || (causal && Tq != Tk)) return FM_ATTN_SHAPE;
+  if (KH < 1 || H % KH != 0) return FM_ATTN_SHAPE;
   for (const void* p : ptrs)
     if (!al16(p)) return FM_ATTN_ALIGN;
-  for (long ld : lds)
+  for (long ld : qlds)
     if (ld % Cfg<T>::VE != 0 || ld < (long)H * dh) return FM_ATTN_ALIGN;
+  for (long ld : kvlds)
+    if (ld % Cfg<T>::VE != 0 || ld < (long)KH * dh) return FM_ATTN_ALIGN;
   return 0;
 }
 
 template <typename T> size_t attn_lds(int dh) { return (size_t)2 * Cfg<T>::KT * (dh + Cfg<T>::PAD) * sizeof(T); }
 
+// query heads of one group that share a forward / dQ block: the largest of 4, 2, 1 dividing G
+int group_share(int G) { return G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1; }
+
+// EXT: lengths or grouped heads; the dense instantiations (EXT false, GS 1) carry none of that code
+template <typename T, int GS, bool EXT>
+void launch_fwd(const T* q, long ldq, const T* k, long ldk, const T* v, long ldv, T* o, long ldo, float* lse,
+                const int* klens, int B, int H, int G, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s) {
+  auto kern = dh == 32 ? fm_attn_fwd<T, 32, GS, EXT> : dh == 64 ? fm_attn_fwd<T, 64, GS, EXT> : fm_attn_fwd<T, 128, GS, EXT>;
+  hipLaunchKernelGGL(kern, dim3((Tq * GS + 127) / 128, H / GS, B), dim3(256), attn_lds<T>(dh), s, q, ldq, k, ldk, v, ldv, o,
+                     ldo, lse, klens, H, G, Tq, Tk, causal, scale * LOG2E);
+}
+
+template <typename T, int GS, bool EXT>
+void launch_dq(const T* q, long ldq, const T* k, long ldk, const T* v, long ldv, const T* o, long ldo, const T* dout,
+               long lddo, const float* lse, T* dq, long lddq, int add, const int* klens, int B, int H, int G, int dh, int Tq,
+               int Tk, int causal, float scale, hipStream_t s) {
+  auto kern = dh == 32 ? fm_attn_dq<T, 32, GS, EXT> : dh == 64 ? fm_attn_dq<T, 64, GS, EXT> : fm_attn_dq<T, 128, GS, EXT>;
+  hipLaunchKernelGGL(kern, dim3((Tq * GS + 127) / 128, H / GS, B), dim3(256), attn_lds<T>(dh), s, q, ldq, k, ldk, v, ldv, o,
+                     ldo, dout, lddo, lse, dq, lddq, add, klens, H, G, Tq, Tk, causal, scale);
+}
+
 template <typename T>
 int attn_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, float* lse, int B,
-             int H, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s) {
-  if (int st = attn_status<T>(B, H, dh, Tq, Tk, causal, {q, k, v, o}, {ldq, ldk, ldv, ldo})) return st;
-  auto kern = dh == 32 ? fm_attn_fwd<T, 32> : dh == 64 ? fm_attn_fwd<T, 64> : fm_attn_fwd<T, 128>;
-  hipLaunchKernelGGL(kern, dim3((Tq + 127) / 128, H, B), dim3(256), attn_lds<T>(dh), s, (const T*)q, ldq, (const T*)k, ldk,
-                     (const T*)v, ldv, (T*)o, ldo, lse, H, Tq, Tk, causal, scale * LOG2E);
+             int H, int KH, int dh, int Tq, int Tk, const int* klens, int causal, float scale, hipStream_t s) {
+  if (int st = attn_status<T>(B, H, KH, dh, Tq, Tk, causal, {q, k, v, o}, {ldq, ldo}, {ldk, ldv})) return st;
+  const int G = H / KH, gs = group_share(G);
+  auto run = !(klens || G > 1) ? launch_fwd<T, 1, false>
+             : gs == 4         ? launch_fwd<T, 4, true>
+             : gs == 2         ? launch_fwd<T, 2, true>
+                               : launch_fwd<T, 1, true>;
+  run((const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (T*)o, ldo, lse, klens, B, H, G, dh, Tq, Tk, causal, scale, s);
   return 0;
 }
 
 template <typename T>
 int attn_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* o, long ldo,
              const void* dout, long lddo, const float* lse, void* dq, long lddq, void* dk, long lddk, void* dv, long lddv,
-             int acc_mask, int B, int H, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s) {
+             int acc_mask, int B, int H, int KH, int dh, int Tq, int Tk, const int* klens, int causal, float scale,
+             hipStream_t s) {
   const long need = (long)H * dh;    // a gradient that is absent has no stride to check
-  if (int st = attn_status<T>(B, H, dh, Tq, Tk, causal, {q, k, v, o, dout, dq, dk, dv},
-                              {ldq, ldk, ldv, ldo, lddo, dq ? lddq : need, dk ? lddk : need, dv ? lddv : need}))
+  if (int st = attn_status<T>(B, H, KH, dh, Tq, Tk, causal, {q, k, v, o, dout, dq, dk, dv},
+                              {ldq, ldo, lddo, dq ? lddq : need}, {ldk, ldv, dk ? lddk : need, dv ? lddv : need}))
     return st;
+  const int G = H / KH, gs = group_share(G);
+  const bool ext = klens != nullptr || G > 1;
   if (dq != nullptr) {
-    auto kern = dh == 32 ? fm_attn_dq<T, 32> : dh == 64 ? fm_attn_dq<T, 64> : fm_attn_dq<T, 128>;
-    hipLaunchKernelGGL(kern, dim3((Tq + 127) / 128, H, B), dim3(256), attn_lds<T>(dh), s, (const T*)q, ldq, (const T*)k, ldk,
-                       (const T*)v, ldv, (const T*)o, ldo, (const T*)dout, lddo, lse, (T*)dq, lddq, acc_mask & 1, H, Tq, Tk,
-                       causal, scale);
+    auto run = !ext    ? launch_dq<T, 1, false>
+               : gs == 4 ? launch_dq<T, 4, true>
+               : gs == 2 ? launch_dq<T, 2, true>
+                         : launch_dq<T, 1, true>;
+    run((const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (const T*)o, ldo, (const T*)dout, lddo, lse, (T*)dq, lddq,
+        acc_mask & 1, klens, B, H, G, dh, Tq, Tk, causal, scale, s);
   }
   if (dk != nullptr || dv != nullptr) {
-    auto kern = dh == 32 ? fm_attn_dkv<T, 32> : dh == 64 ? fm_attn_dkv<T, 64> : fm_attn_dkv<T, 128>;
-    hipLaunchKernelGGL(kern, dim3((Tk + 127) / 128, H, B), dim3(256), attn_lds<T>(dh) + 2 * Cfg<T>::KT * sizeof(float), s,
+    auto kern = dh == 32 ? fm_attn_dkv<T, 32, true> : dh == 64 ? fm_attn_dkv<T, 64, true> : fm_attn_dkv<T, 128, true>;
+    if (!ext) kern = dh == 32 ? fm_attn_dkv<T, 32, false> : dh == 64 ? fm_attn_dkv<T, 64, false> : fm_attn_dkv<T, 128, false>;
+    hipLaunchKernelGGL(kern, dim3((Tk + 127) / 128, KH, B), dim3(256), attn_lds<T>(dh) + 2 * Cfg<T>::KT * sizeof(float), s,
                        (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (const T*)o, ldo, (const T*)dout, lddo, lse,
-                       (T*)dk, lddk, (T*)dv, lddv, (acc_mask >> 1) & 1, (acc_mask >> 2) & 1, H, Tq, Tk, causal, scale);
+                       (T*)dk, lddk, (T*)dv, lddv, (acc_mask >> 1) & 1, (acc_mask >> 2) & 1, klens, H, G, Tq, Tk, causal,
+                       scale);
   }
   return 0;
 }
@@ -507,35 +585,37 @@ int attn_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, lo
 extern "C" void fm_attention_error(int status, const char** msg) {
   *msg = status == 0                  ? "ok"
          : status == FM_ATTN_HEAD_DIM ? "attention: head dimension 32, 64 or 128"
-         : status == FM_ATTN_SHAPE    ? "attention: 1..65535 samples and heads, Tq, Tk >= 1, causal needs Tq == Tk"
+         : status == FM_ATTN_SHAPE    ? "attention: 1..65535 samples and heads, Tq, Tk >= 1, causal needs Tq == Tk, kv_heads "
+                                        "must divide heads"
          : status == FM_ATTN_ALIGN    ? "attention: 16-byte aligned bases and row strides (ld % 8 for bf16, ld % 4 for "
-                                        "fp32), row strides of at least heads * dh"
+                                        "fp32), row strides of at least heads * dh (kv_heads * dh for k, v, dk, dv)"
                                       : "attention: unknown status";
 }
 
 extern "C" int fm_attention_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo,
-                                float* lse, int B, int H, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s) {
-  return attn_fwd<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, dh, Tq, Tk, causal, scale, s);
+                                float* lse, int B, int H, int KH, int dh, int Tq, int Tk, const int* key_lengths, int causal,
+                                float scale, hipStream_t s) {
+  return attn_fwd<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, KH, dh, Tq, Tk, key_lengths, causal, scale, s);
 }
 
 extern "C" int fm_attention_fwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
-                                    long ldo, float* lse, int B, int H, int dh, int Tq, int Tk, int causal, float scale,
-                                    hipStream_t s) {
-  return attn_fwd<float>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, dh, Tq, Tk, causal, scale, s);
+                                    long ldo, float* lse, int B, int H, int KH, int dh, int Tq, int Tk,
+                                    const int* key_lengths, int causal, float scale, hipStream_t s) {
+  return attn_fwd<float>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, KH, dh, Tq, Tk, key_lengths, causal, scale, s);
 }
 
 extern "C" int fm_attention_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* o,
                                 long ldo, const void* dout, long lddo, const float* lse, void* dq, long lddq, void* dk,
-                                long lddk, void* dv, long lddv, int acc_mask, int B, int H, int dh, int Tq, int Tk,
-                                int causal, float scale, hipStream_t s) {
-  return attn_bwd<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, acc_mask, B, H, dh,
-                          Tq, Tk, causal, scale, s);
+                                long lddk, void* dv, long lddv, int acc_mask, int B, int H, int KH, int dh, int Tq, int Tk,
+                                const int* key_lengths, int causal, float scale, hipStream_t s) {
+  return attn_bwd<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, acc_mask, B, H, KH,
+                          dh, Tq, Tk, key_lengths, causal, scale, s);
 }
 
 extern "C" int fm_attention_bwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv,
                                     const float* o, long ldo, const float* dout, long lddo, const float* lse, float* dq,
-                                    long lddq, float* dk, long lddk, float* dv, long lddv, int acc_mask, int B, int H, int dh,
-                                    int Tq, int Tk, int causal, float scale, hipStream_t s) {
-  return attn_bwd<float>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, acc_mask, B, H, dh,
-                         Tq, Tk, causal, scale, s);
+                                    long lddq, float* dk, long lddk, float* dv, long lddv, int acc_mask, int B, int H, int KH,
+                                    int dh, int Tq, int Tk, const int* key_lengths, int causal, float scale, hipStream_t s) {
+  return attn_bwd<float>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, acc_mask, B, H, KH,
+                         dh, Tq, Tk, key_lengths, causal, scale, s);
 }

@@ -304,19 +304,24 @@ class FFModel:
         t = self.dense(v, D, ActiMode.AC_MODE_NONE, True, None, uinit, bias_initializer or ZeroInitializer(), pre("u"))
         return self.cross_combine(x0, t, None if x is x0 else x, name)
 
-    def attention(self, q, k, v, heads, causal=False, scale=None, name=None):
+    def attention(self, q, k, v, heads, causal=False, scale=None, name=None, kv_heads=None, key_lengths=None):
         """Fused attention core ``softmax(scale q k^T + mask) v`` per head on ``[B, T, heads * dh]``
         tensors (:class:`flexmi.ops.attention.Attention`); ``scale`` defaults to ``1 / sqrt(dh)``,
-        ``causal`` needs ``Tq == Tk``.  The three inputs must be three tensors."""
-        return self._add(Attention(self, q, k, v, heads, causal, scale, name)).outputs[0]
+        ``causal`` needs ``Tq == Tk``.  The three inputs must be three tensors.  ``kv_heads`` (default
+        ``heads``, must divide it): ``k`` / ``v`` are ``[B, Tk, kv_heads * dh]`` and each of their heads
+        serves ``heads // kv_heads`` query heads.  ``key_lengths``: an int32 tensor ``[B, 1]``, key ``j``
+        of sample ``b`` is visible iff ``j < key_lengths[b]`` (clamped into ``[0, Tk]``)."""
+        return self._add(Attention(self, q, k, v, heads, causal, scale, name, kv_heads, key_lengths)).outputs[0]
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, bias=True, causal=False,
-                            kernel_initializer=None, name=None, fp8=None):
+                            kernel_initializer=None, name=None, fp8=None, num_kv_heads=None, key_lengths=None):
         """Multi-head attention on ``query [B, Tq, *]``, ``key`` / ``value [B, Tk, *]``: four ordinary
         Linear ops ``<name>_q/_k/_v/_o`` (no activation, Glorot-uniform kernels as :meth:`dense`, zero
         bias) with the fused :meth:`attention` between them; ``kdim`` / ``vdim`` are checked against
         the inputs' widths when given.  Passing one tensor as query, key and value is
-        self-attention: the projections make three tensors of it.
+        self-attention: the projections make three tensors of it.  ``num_kv_heads`` (grouped-query
+        attention): ``<name>_k`` / ``<name>_v`` are ``num_kv_heads * embed_dim // num_heads`` wide;
+        ``key_lengths`` (int32 ``[B, 1]``) is ``key_padding_mask`` given as the count of real keys.
 
         Weights map to ``torch.nn.MultiheadAttention(embed_dim, num_heads, batch_first=True)`` with
         ``E = embed_dim``: ``<name>_q.weight = in_proj_weight[0:E]``, ``<name>_k.weight =
@@ -329,11 +334,15 @@ class FFModel:
                 raise ValueError(f"multihead_attention: {what} = {d} but the tensor has {t.dims[-1]} features")
         if embed_dim % num_heads != 0:
             raise ValueError(f"multihead_attention: embed_dim {embed_dim} is not a multiple of num_heads {num_heads}")
+        kv_heads = num_heads if num_kv_heads is None else int(num_kv_heads)
+        if kv_heads < 1 or num_heads % kv_heads != 0:
+            raise ValueError(f"multihead_attention: num_kv_heads {kv_heads} does not divide num_heads {num_heads}")
         pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
-        proj = lambda t, s: self.dense(t, embed_dim, ActiMode.AC_MODE_NONE, bias, None, kernel_initializer, None,  # noqa: E731
-                                       pre(s), fp8)
-        q, k, v = proj(query, "q"), proj(key, "k"), proj(value, "v")
-        return proj(self.attention(q, k, v, num_heads, causal, None, name), "o")
+        proj = lambda t, s, width=embed_dim: self.dense(t, width, ActiMode.AC_MODE_NONE, bias, None,  # noqa: E731
+                                                        kernel_initializer, None, pre(s), fp8)
+        kv_width = embed_dim // num_heads * kv_heads
+        q, k, v = proj(query, "q"), proj(key, "k", kv_width), proj(value, "v", kv_width)
+        return proj(self.attention(q, k, v, num_heads, causal, None, name, kv_heads, key_lengths), "o")
 
     def layer_norm(self, x, residual=None, eps=1e-5, elementwise_affine=True, rms=False, name=None):
         """LayerNorm over the last dim of ``x [..., D]`` (:class:`flexmi.ops.norm.LayerNorm`), of ``x +
@@ -343,7 +352,7 @@ class FFModel:
         return self._add(LayerNorm(self, x, residual, eps, elementwise_affine, rms, name)).outputs[0]
 
     def transformer_encoder_layer(self, x, num_heads, dim_feedforward, causal=False, norm_first=False, name=None,
-                                  attention_bias=True, fp8=None):
+                                  attention_bias=True, fp8=None, num_kv_heads=None, key_lengths=None):
         """One transformer encoder layer on ``x [B, T, E]`` without dropout: self-attention
         (:meth:`multihead_attention`, ``<name>_attn``), a feed-forward of two :meth:`dense` ops
         ``<name>_ff1`` (ReLU, ``dim_feedforward`` wide) and ``<name>_ff2``, and two :meth:`layer_norm` ops
@@ -351,7 +360,7 @@ class FFModel:
         layer_norm(attn(x), residual=x)``, ``out = layer_norm(ffn(h), residual=h)``.  ``norm_first``:
         ``h = x + attn(layer_norm(x))``, ``out = h + ffn(layer_norm(h))`` with the plain :meth:`add`.
         ``attention_bias=False`` builds the four attention projections without bias; ``fp8`` goes to all six
-        :meth:`dense` calls.
+        :meth:`dense` calls; ``num_kv_heads`` and ``key_lengths`` go to :meth:`multihead_attention`.
 
         Weights map to ``torch.nn.TransformerEncoderLayer(E, num_heads, dim_feedforward, dropout=0,
         batch_first=True, norm_first=norm_first)``: ``<name>_attn_q/_k/_v/_o`` to ``self_attn`` as
@@ -361,7 +370,8 @@ class FFModel:
         E = x.dims[-1]
         pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
         attn = lambda t: self.multihead_attention(t, t, t, E, num_heads, bias=attention_bias, causal=causal,  # noqa: E731
-                                                  name=pre("attn"), fp8=fp8)
+                                                  name=pre("attn"), fp8=fp8, num_kv_heads=num_kv_heads,
+                                                  key_lengths=key_lengths)
         ffn = lambda t: self.dense(self.dense(t, dim_feedforward, ActiMode.AC_MODE_RELU, name=pre("ff1"), fp8=fp8), E,  # noqa: E731
                                    name=pre("ff2"), fp8=fp8)
         if norm_first:

@@ -33,7 +33,8 @@ def _make_clone(op, m, in_shapes, out_shapes):
     elif t == OperatorType.OP_CROSS_COMBINE:
         m.cross_combine(ins[0], ins[1], ins[2] if len(ins) > 2 else None)
     elif t == OperatorType.OP_ATTENTION:
-        m.attention(ins[0], ins[1], ins[2], op.heads, op.causal, op.scale)
+        m.attention(ins[0], ins[1], ins[2], op.heads, op.causal, op.scale, kv_heads=op.kv_heads,
+                    key_lengths=ins[3] if op.has_lengths else None)
     elif t == OperatorType.OP_LAYERNORM:
         m.layer_norm(ins[0], ins[1] if len(ins) > 1 else None, op.eps, op.affine, op.rms)
     elif t == OperatorType.OP_CONCAT:
