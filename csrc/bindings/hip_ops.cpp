@@ -774,9 +774,19 @@ const int* attn_lengths(const c10::optional<torch::Tensor>& len, int64_t B) {
   return len->data_ptr<int>();
 }
 
-// k, v (and dk, dv) are [B, Tk, kv_heads * dh]; key_lengths: see launchers.h
+// null without a rotary table; else fp32, contiguous, on the device, a row of dh for each of max(Tq, Tk) positions
+const float* attn_rope(const c10::optional<torch::Tensor>& rope, int64_t positions, int64_t dh) {
+  if (!given(rope)) return nullptr;
+  TORCH_CHECK(rope->is_cuda() && rope->scalar_type() == torch::kFloat32 && rope->is_contiguous() && rope->dim() == 2 &&
+                  rope->size(0) >= positions && rope->size(1) == dh,
+              "attention rope: contiguous fp32 device table [>= max(Tq, Tk), dh] of cos | sin rows");
+  return rope->data_ptr<float>();
+}
+
+// k, v (and dk, dv) are [B, Tk, kv_heads * dh]; key_lengths, rope: see launchers.h
 void attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor out, torch::Tensor lse, int64_t heads,
-              bool causal, double scale, int64_t kv_heads, c10::optional<torch::Tensor> key_lengths) {
+              bool causal, double scale, int64_t kv_heads, c10::optional<torch::Tensor> key_lengths,
+              c10::optional<torch::Tensor> rope, bool rope_interleaved) {
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 || q.scalar_type() == torch::kFloat32, "attention: bf16 or fp32");
   TORCH_CHECK(q.dim() == 3 && heads >= 1 && q.size(2) % heads == 0, "attention: q [B, Tq, heads * dh]");
   TORCH_CHECK(kv_heads >= 1 && heads % kv_heads == 0, "attention: kv_heads must divide heads");
@@ -785,21 +795,23 @@ void attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o
                 ldv = attn_operand(v, q, Tk, Ek, "v"), ldo = attn_operand(out, q, Tq, E, "out");
   attn_lse_check(lse, B * heads * Tq);
   const int* len = attn_lengths(key_lengths, B);
+  const float* rp = attn_rope(rope, std::max(Tq, Tk), E / heads);
+  const int ri = rope_interleaved ? 1 : 0;
   if (q.scalar_type() == torch::kFloat32)
     attn_check(fm_attention_fwd_f32(q.data_ptr<float>(), ldq, k.data_ptr<float>(), ldk, v.data_ptr<float>(), ldv,
                                     out.data_ptr<float>(), ldo, lse.data_ptr<float>(), (int)B, (int)heads, (int)kv_heads,
-                                    (int)(E / heads), (int)Tq, (int)Tk, len, causal ? 1 : 0, (float)scale, cur()));
+                                    (int)(E / heads), (int)Tq, (int)Tk, len, causal ? 1 : 0, (float)scale, rp, ri, cur()));
   else
     attn_check(fm_attention_fwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo,
                                 lse.data_ptr<float>(), (int)B, (int)heads, (int)kv_heads, (int)(E / heads), (int)Tq, (int)Tk,
-                                len, causal ? 1 : 0, (float)scale, cur()));
+                                len, causal ? 1 : 0, (float)scale, rp, ri, cur()));
 }
 
 // acc_mask bit 0 / 1 / 2: dq / dk / dv are added to; an absent gradient is not computed
 void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor out, torch::Tensor dout, torch::Tensor lse,
               c10::optional<torch::Tensor> dq, c10::optional<torch::Tensor> dk, c10::optional<torch::Tensor> dv,
               int64_t acc_mask, int64_t heads, bool causal, double scale, int64_t kv_heads,
-              c10::optional<torch::Tensor> key_lengths) {
+              c10::optional<torch::Tensor> key_lengths, c10::optional<torch::Tensor> rope, bool rope_interleaved) {
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 || q.scalar_type() == torch::kFloat32, "attention: bf16 or fp32");
   TORCH_CHECK(q.dim() == 3 && heads >= 1 && q.size(2) % heads == 0, "attention: q [B, Tq, heads * dh]");
   TORCH_CHECK(kv_heads >= 1 && heads % kv_heads == 0, "attention: kv_heads must divide heads");
@@ -811,17 +823,19 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor o
                 lddv = given(dv) ? attn_operand(*dv, q, Tk, Ek, "dv") : 0;
   attn_lse_check(lse, B * heads * Tq);
   const int* len = attn_lengths(key_lengths, B);
+  const float* rp = attn_rope(rope, std::max(Tq, Tk), E / heads);
+  const int ri = rope_interleaved ? 1 : 0;
   if (q.scalar_type() == torch::kFloat32)
     attn_check(fm_attention_bwd_f32(q.data_ptr<float>(), ldq, k.data_ptr<float>(), ldk, v.data_ptr<float>(), ldv,
                                     out.data_ptr<float>(), ldo, dout.data_ptr<float>(), lddo, lse.data_ptr<float>(),
                                     (float*)mptr(dq), lddq, (float*)mptr(dk), lddk, (float*)mptr(dv), lddv, (int)acc_mask,
                                     (int)B, (int)heads, (int)kv_heads, (int)(E / heads), (int)Tq, (int)Tk, len, causal ? 1 : 0,
-                                    (float)scale, cur()));
+                                    (float)scale, rp, ri, cur()));
   else
     attn_check(fm_attention_bwd(q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, out.data_ptr(), ldo, dout.data_ptr(),
                                 lddo, lse.data_ptr<float>(), mptr(dq), lddq, mptr(dk), lddk, mptr(dv), lddv, (int)acc_mask,
                                 (int)B, (int)heads, (int)kv_heads, (int)(E / heads), (int)Tq, (int)Tk, len, causal ? 1 : 0,
-                                (float)scale, cur()));
+                                (float)scale, rp, ri, cur()));
 }
 
 // ---- LayerNorm / RMSNorm with fused residual (layernorm.hip) -----------------------------------------

@@ -111,6 +111,87 @@ template <int DH> FM_DEVICE float dot_frag(const Frag<float, DH>& a, const Frag<
   return s;
 }
 
+// ---- rotary position embedding ------------------------------------------------------------------------
+// tab is fp32 [positions][DH]: row t holds cos(t w_i), i < DH/2, then sin(t w_i), computed on the host.  A row's
+// column pairs (lo, hi) are (i, i + DH/2) (half-split) or (2i, 2i + 1) (inter, a wave-uniform runtime flag):
+// lo' = lo c - hi s, hi' = hi c + lo s in fp32, rounded to storage once.  The transpose, which takes dq and dk
+// back, is the same with -s.  Every access below is an aligned 8 or 16 bytes of one table row.
+FM_DEVICE void rot(float& lo, float& hi, float c, float s) {
+  const float x = lo * c - hi * s;
+  hi = hi * c + lo * s;
+  lo = x;
+}
+template <int N> FM_DEVICE void ldf(float (&d)[N], const float* __restrict__ p) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  if constexpr (N == 2) {
+    const f32x2_t t = *reinterpret_cast<const f32x2_t*>(p);
+    d[0] = t[0], d[1] = t[1];
+  } else {
+#pragma unroll
+    for (int j = 0; j < N / 4; ++j) {
+      const f32x4_t t = *reinterpret_cast<const f32x4_t*>(p + 4 * j);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) d[4 * j + e] = t[e];
+    }
+  }
+}
+
+// a register-resident row at position tr = tab + t DH.  bf16 holds both columns of a pair in one lane:
+// v[ks] with v[ks + DH/32], or elements e, e + 1
+template <int DH> FM_DEVICE void rope_frag(Frag<bf16_t, DH>& f, const float* __restrict__ tr, int inter, int h) {
+  if (inter) {
+#pragma unroll
+    for (int ks = 0; ks < DH / 16; ++ks) {                         // columns 16 ks + 8 h + e: frequencies 8 ks + 4 h + e / 2
+      float c[4], s[4];
+      ldf(c, tr + 8 * ks + 4 * h);
+      ldf(s, tr + DH / 2 + 8 * ks + 4 * h);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        float lo = bf2f((bf16_t)f.v[ks][2 * p]), hi = bf2f((bf16_t)f.v[ks][2 * p + 1]);
+        rot(lo, hi, c[p], s[p]);
+        f.v[ks][2 * p] = (short)f2bf(lo), f.v[ks][2 * p + 1] = (short)f2bf(hi);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int ks = 0; ks < DH / 32; ++ks) {
+      float c[8], s[8];
+      ldf(c, tr + 16 * ks + 8 * h);
+      ldf(s, tr + DH / 2 + 16 * ks + 8 * h);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float lo = bf2f((bf16_t)f.v[ks][e]), hi = bf2f((bf16_t)f.v[ks + DH / 32][e]);
+        rot(lo, hi, c[e], s[e]);
+        f.v[ks][e] = (short)f2bf(lo), f.v[ks + DH / 32][e] = (short)f2bf(hi);
+      }
+    }
+  }
+}
+// fp32: lane half h holds column h DH/2 + ks, so an interleaved pair is (v[ks], v[ks + 1]) and the half-split
+// partner of v[ks] is the other half-wave's v[ks] (half 0 holds lo, half 1 hi)
+template <int DH> FM_DEVICE void rope_frag(Frag<float, DH>& f, const float* __restrict__ tr, int inter, int h) {
+  if (inter) {
+#pragma unroll
+    for (int j = 0; j < DH / 8; ++j) {
+      float c[2], s[2];
+      ldf(c, tr + h * (DH / 4) + 2 * j);
+      ldf(s, tr + DH / 2 + h * (DH / 4) + 2 * j);
+      rot(f.v[4 * j], f.v[4 * j + 1], c[0], s[0]);
+      rot(f.v[4 * j + 2], f.v[4 * j + 3], c[1], s[1]);
+    }
+  } else {
+    const float sg = h ? 1.f : -1.f;
+#pragma unroll
+    for (int j = 0; j < DH / 8; ++j) {
+      float c[4], s[4];
+      ldf(c, tr + 4 * j);
+      ldf(s, tr + DH / 2 + 4 * j);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f.v[4 * j + e] = f.v[4 * j + e] * c[e] + sg * s[e] * other_half(f.v[4 * j + e]);
+    }
+  }
+}
+
 #define FM_ATTN_MFMA_BF16(a, b, c) \
   __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8v_t, a), __builtin_bit_cast(bf16x8v_t, b), c, 0, 0, 0)
 
@@ -174,6 +255,53 @@ template <typename T, int DH, int NR> struct Stage {
       v[t] = gr < nrows ? *reinterpret_cast<const u32x4_t*>(base + (long)gr * ld + (c % CPR) * VE) : u32x4_t{0u, 0u, 0u, 0u};
     }
   }
+  // the loaded rows rotated on their way to LDS, row row0 + c / CPR at its own position.  An interleaved pair lies
+  // inside a chunk, the half-split partner chunk is CPR / 2 lanes away in the same wave.  Rows >= nrows (>= 1) are
+  // zeros and stay zeros: they read the last row of the table, the rotation of zeros is zero.
+  FM_DEVICE void rope(const float* __restrict__ tab, int row0, int nrows, int tid, int inter) {
+#pragma unroll
+    for (int t = 0; t < NCH; ++t) {
+      const int c = tid + 256 * t, col = (c % CPR) * VE;
+      const float* tr = tab + (long)min(row0 + c / CPR, nrows - 1) * DH;
+      float x[VE];
+      unpack(x, v[t]);
+      if (inter) {
+        float cs[VE / 2], sn[VE / 2];
+        ldf(cs, tr + col / 2);
+        ldf(sn, tr + DH / 2 + col / 2);
+#pragma unroll
+        for (int p = 0; p < VE / 2; ++p) rot(x[2 * p], x[2 * p + 1], cs[p], sn[p]);
+      } else {
+        u32x4_t pv;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pv[e] = __shfl_xor(v[t][e], CPR / 2, 64);
+        const float sg = col < DH / 2 ? -1.f : 1.f;
+        float y[VE], cs[VE], sn[VE];
+        unpack(y, pv);
+        ldf(cs, tr + col % (DH / 2));
+        ldf(sn, tr + DH / 2 + col % (DH / 2));
+#pragma unroll
+        for (int e = 0; e < VE; ++e) x[e] = x[e] * cs[e] + sg * sn[e] * y[e];
+      }
+      v[t] = pack(x);
+    }
+  }
+  static FM_DEVICE void unpack(float (&x)[VE], const u32x4_t& a) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if constexpr (VE == 8) x[2 * e] = __uint_as_float(a[e] << 16), x[2 * e + 1] = __uint_as_float(a[e] & 0xffff0000u);
+      else x[e] = __uint_as_float(a[e]);
+    }
+  }
+  static FM_DEVICE u32x4_t pack(const float (&x)[VE]) {
+    u32x4_t a;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if constexpr (VE == 8) a[e] = (unsigned)f2bf(x[2 * e]) | ((unsigned)f2bf(x[2 * e + 1]) << 16);
+      else a[e] = __float_as_uint(x[e]);
+    }
+    return a;
+  }
   FM_DEVICE void store(T* tile, int tid) const {
 #pragma unroll
     for (int t = 0; t < NCH; ++t) {
@@ -226,17 +354,53 @@ template <typename T, int DH> FM_DEVICE void store_rows(const f32x16_t (&acc)[DH
     }
 }
 
+// dq / dk of the rotated rows taken back through the transpose of the rotation at tr, in the fp32 accumulators,
+// before store_rows rounds them.  The lane holds columns 8 i + 4 h + e of its row in acc[i / 4][4 (i % 4) + e]:
+// the half-split partner (+ DH/2) is i + DH/16 of the same lane, the interleaved one e ^ 1.
+template <int DH> FM_DEVICE void unrope_acc(f32x16_t (&acc)[DH / 32], const float* __restrict__ tr, int inter, int h) {
+  constexpr int NI = DH / 8;
+  if (inter) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      float c[2], s[2];
+      ldf(c, tr + 4 * i + 2 * h);
+      ldf(s, tr + DH / 2 + 4 * i + 2 * h);
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        float lo = acc[i / 4][4 * (i % 4) + 2 * p], hi = acc[i / 4][4 * (i % 4) + 2 * p + 1];
+        rot(lo, hi, c[p], -s[p]);
+        acc[i / 4][4 * (i % 4) + 2 * p] = lo, acc[i / 4][4 * (i % 4) + 2 * p + 1] = hi;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NI / 2; ++i) {
+      constexpr int J = NI / 2;
+      float c[4], s[4];
+      ldf(c, tr + 8 * i + 4 * h);
+      ldf(s, tr + DH / 2 + 8 * i + 4 * h);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float lo = acc[i / 4][4 * (i % 4) + e], hi = acc[(i + J) / 4][4 * ((i + J) % 4) + e];
+        rot(lo, hi, c[e], -s[e]);
+        acc[i / 4][4 * (i % 4) + e] = lo, acc[(i + J) / 4][4 * ((i + J) % 4) + e] = hi;
+      }
+    }
+  }
+}
+
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
 // the keys of sample b that take part (block-uniform)
 FM_DEVICE int key_count(const int* __restrict__ klens, int b, int Tk) { return klens ? min(max(klens[b], 0), Tk) : Tk; }
 
 // ---- forward ---------------------------------------------------------------------------------------
-template <typename T, int DH, int GS, bool EXT>
+template <typename T, int DH, int GS, bool EXT, bool ROPE>
 __global__ void __launch_bounds__(256) fm_attn_fwd(const T* __restrict__ q, long ldq, const T* __restrict__ k, long ldk,
                                                    const T* __restrict__ v, long ldv, T* __restrict__ o, long ldo,
-                                                   float* __restrict__ lse, const int* __restrict__ klens, int H, int G,
-                                                   int Tq, int Tk, int causal, float sc2) {
+                                                   float* __restrict__ lse, const int* __restrict__ klens,
+                                                   const float* __restrict__ rope, int inter, int H, int G, int Tq, int Tk,
+                                                   int causal, float sc2) {
   constexpr int KT = Cfg<T>::KT, LD = DH + Cfg<T>::PAD, NT = DH / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* ks = reinterpret_cast<T*>(smem);
@@ -253,6 +417,7 @@ __global__ void __launch_bounds__(256) fm_attn_fwd(const T* __restrict__ q, long
   const bool active = q0 < Tq;                                   // wave-uniform
   Frag<T, DH> qf;
   load_frag(qf, q + (long)min(qi, Tq - 1) * ldq, h);
+  if (ROPE) rope_frag(qf, rope + (long)min(qi, Tq - 1) * DH, inter, h);
   f32x16_t acc[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
@@ -265,6 +430,7 @@ __global__ void __launch_bounds__(256) fm_attn_fwd(const T* __restrict__ q, long
   sk.load(k, ldk, 0, klen, tid);
   sv.load(v, ldv, 0, klen, tid);
   for (int kt = 0; kt < nkt; ++kt) {
+    if (ROPE) sk.rope(rope, kt * KT, klen, tid, inter);          // in registers, while the V loads are still in flight
     __syncthreads();                                             // the previous tile has been read
     sk.store(ks, tid);
     sv.store(vs, tid);
@@ -327,12 +493,13 @@ __global__ void __launch_bounds__(256) fm_attn_fwd(const T* __restrict__ q, long
 }
 
 // ---- backward: dQ ------------------------------------------------------------------------------------
-template <typename T, int DH, int GS, bool EXT>
+template <typename T, int DH, int GS, bool EXT, bool ROPE>
 __global__ void __launch_bounds__(256) fm_attn_dq(const T* __restrict__ q, long ldq, const T* __restrict__ k, long ldk,
                                                   const T* __restrict__ v, long ldv, const T* __restrict__ o, long ldo,
                                                   const T* __restrict__ dout, long lddo, const float* __restrict__ lse,
                                                   T* __restrict__ dq, long lddq, int add, const int* __restrict__ klens,
-                                                  int H, int G, int Tq, int Tk, int causal, float scale) {
+                                                  const float* __restrict__ rope, int inter, int H, int G, int Tq, int Tk,
+                                                  int causal, float scale) {
   constexpr int KT = Cfg<T>::KT, LD = DH + Cfg<T>::PAD, NT = DH / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* ks = reinterpret_cast<T*>(smem);
@@ -352,6 +519,7 @@ __global__ void __launch_bounds__(256) fm_attn_dq(const T* __restrict__ q, long 
   const bool active = q0 < Tq;
   Frag<T, DH> qf, dof;
   load_frag(qf, q + (long)qc * ldq, h);
+  if (ROPE) rope_frag(qf, rope + (long)qc * DH, inter, h);
   load_frag(dof, dout + (long)qc * lddo, h);
   float delta;
   {
@@ -372,6 +540,7 @@ __global__ void __launch_bounds__(256) fm_attn_dq(const T* __restrict__ q, long 
   sk.load(k, ldk, 0, klen, tid);
   sv.load(v, ldv, 0, klen, tid);
   for (int kt = 0; kt < nkt; ++kt) {
+    if (ROPE) sk.rope(rope, kt * KT, klen, tid, inter);
     __syncthreads();
     sk.store(ks, tid);
     sv.store(vs, tid);
@@ -398,17 +567,20 @@ __global__ void __launch_bounds__(256) fm_attn_dq(const T* __restrict__ q, long 
       mma_acc<DH>(acc, ks + 32 * t * LD, s, lane);
     }
   }
-  if (active && qi < Tq) store_rows<T, DH>(acc, dq + (long)qi * lddq, 1.f, add != 0, h);
+  if (active && qi < Tq) {
+    if (ROPE) unrope_acc<DH>(acc, rope + (long)qi * DH, inter, h);
+    store_rows<T, DH>(acc, dq + (long)qi * lddq, 1.f, add != 0, h);
+  }
 }
 
 // ---- backward: dK and dV -------------------------------------------------------------------------------
-template <typename T, int DH, bool EXT>
+template <typename T, int DH, bool EXT, bool ROPE>
 __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long ldq, const T* __restrict__ k, long ldk,
                                                    const T* __restrict__ v, long ldv, const T* __restrict__ o, long ldo,
                                                    const T* __restrict__ dout, long lddo, const float* __restrict__ lse,
                                                    T* __restrict__ dk, long lddk, T* __restrict__ dv, long lddv, int addk,
-                                                   int addv, const int* __restrict__ klens, int H, int Gq, int Tq, int Tk,
-                                                   int causal, float scale) {
+                                                   int addv, const int* __restrict__ klens, const float* __restrict__ rope,
+                                                   int inter, int H, int Gq, int Tq, int Tk, int causal, float scale) {
   constexpr int QT = Cfg<T>::KT, LD = DH + Cfg<T>::PAD, NT = DH / 32;
   typedef Stage<T, DH, QT> St;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -435,6 +607,7 @@ __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long
   const int kc = EXT ? max(min(kj, klen - 1), 0) : min(kj, Tk - 1);
   Frag<T, DH> kf, vf;
   load_frag(kf, k + (long)kc * ldk, h);
+  if (ROPE) rope_frag(kf, rope + (long)kc * DH, inter, h);       // the position of the row loaded
   load_frag(vf, v + (long)kc * ldv, h);
   f32x16_t acck[NT], accv[NT];
 #pragma unroll
@@ -450,7 +623,7 @@ __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long
     sd.load(dout + gi * DH, lddo, qb, Tq, tid);
     so.load(o + gi * DH, ldo, qb, Tq, tid);
     __syncthreads();                                             // the previous tile has been read
-    sq.store(qs, tid);
+    if (!ROPE) sq.store(qs, tid);
     sd.store(dos, tid);
     // delta of a row: its St::CPR chunks sit in consecutive lanes
 #pragma unroll
@@ -460,6 +633,10 @@ __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long
       for (int off = St::CPR / 2; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
       const int c = tid + 256 * t;
       if (c % St::CPR == 0) dels[c / St::CPR] = d;
+    }
+    if (ROPE) {                                                  // once dO and O are done with, in their registers
+      sq.rope(rope, qb, Tq, tid, inter);
+      sq.store(qs, tid);
     }
     if (tid < QT) lses[tid] = qb + tid < Tq ? (EXT ? lse + (long)gi * Tq : lse)[qb + tid] * LOG2E : 0.f;
     __syncthreads();
@@ -491,8 +668,12 @@ __global__ void __launch_bounds__(256) fm_attn_dkv(const T* __restrict__ q, long
     if (addk) dk = nullptr;
     if (addv) dv = nullptr;
   }
-  if (dk != nullptr) store_rows<T, DH>(acck, dk + ((long)b * Tk + kj) * lddk + kvh * DH, 1.f, addk != 0, h);
+  if (!ROPE && dk != nullptr) store_rows<T, DH>(acck, dk + ((long)b * Tk + kj) * lddk + kvh * DH, 1.f, addk != 0, h);
   if (dv != nullptr) store_rows<T, DH>(accv, dv + ((long)b * Tk + kj) * lddv + kvh * DH, 1.f, addv != 0, h);
+  if (ROPE && dk != nullptr) {                                   // after dv has left its registers: fp32 DH = 128 needs them
+    unrope_acc<DH>(acck, rope + (long)kj * DH, inter, h);
+    store_rows<T, DH>(acck, dk + ((long)b * Tk + kj) * lddk + kvh * DH, 1.f, addk != 0, h);
+  }
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------
@@ -519,34 +700,64 @@ template <typename T> size_t attn_lds(int dh) { return (size_t)2 * Cfg<T>::KT * 
 // query heads of one group that share a forward / dQ block: the largest of 4, 2, 1 dividing G
 int group_share(int G) { return G % 4 == 0 ? 4 : G % 2 == 0 ? 2 : 1; }
 
-// EXT: lengths or grouped heads; the dense instantiations (EXT false, GS 1) carry none of that code
-template <typename T, int GS, bool EXT>
+// EXT: lengths or grouped heads, ROPE: a rotary table; the dense instantiations (both false, GS 1) carry none of that code
+template <typename T, int GS, bool EXT, bool ROPE>
 void launch_fwd(const T* q, long ldq, const T* k, long ldk, const T* v, long ldv, T* o, long ldo, float* lse,
-                const int* klens, int B, int H, int G, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s) {
-  auto kern = dh == 32 ? fm_attn_fwd<T, 32, GS, EXT> : dh == 64 ? fm_attn_fwd<T, 64, GS, EXT> : fm_attn_fwd<T, 128, GS, EXT>;
+                const int* klens, const float* rope, int inter, int B, int H, int G, int dh, int Tq, int Tk, int causal,
+                float scale, hipStream_t s) {
+  auto kern = dh == 32   ? fm_attn_fwd<T, 32, GS, EXT, ROPE>
+              : dh == 64 ? fm_attn_fwd<T, 64, GS, EXT, ROPE>
+                         : fm_attn_fwd<T, 128, GS, EXT, ROPE>;
   hipLaunchKernelGGL(kern, dim3((Tq * GS + 127) / 128, H / GS, B), dim3(256), attn_lds<T>(dh), s, q, ldq, k, ldk, v, ldv, o,
-                     ldo, lse, klens, H, G, Tq, Tk, causal, scale * LOG2E);
+                     ldo, lse, klens, rope, inter, H, G, Tq, Tk, causal, scale * LOG2E);
 }
 
-template <typename T, int GS, bool EXT>
+template <typename T, int GS, bool EXT, bool ROPE>
 void launch_dq(const T* q, long ldq, const T* k, long ldk, const T* v, long ldv, const T* o, long ldo, const T* dout,
-               long lddo, const float* lse, T* dq, long lddq, int add, const int* klens, int B, int H, int G, int dh, int Tq,
-               int Tk, int causal, float scale, hipStream_t s) {
-  auto kern = dh == 32 ? fm_attn_dq<T, 32, GS, EXT> : dh == 64 ? fm_attn_dq<T, 64, GS, EXT> : fm_attn_dq<T, 128, GS, EXT>;
+               long lddo, const float* lse, T* dq, long lddq, int add, const int* klens, const float* rope, int inter, int B,
+               int H, int G, int dh, int Tq, int Tk, int causal, float scale, hipStream_t s) {
+  auto kern = dh == 32   ? fm_attn_dq<T, 32, GS, EXT, ROPE>
+              : dh == 64 ? fm_attn_dq<T, 64, GS, EXT, ROPE>
+                         : fm_attn_dq<T, 128, GS, EXT, ROPE>;
   hipLaunchKernelGGL(kern, dim3((Tq * GS + 127) / 128, H / GS, B), dim3(256), attn_lds<T>(dh), s, q, ldq, k, ldk, v, ldv, o,
-                     ldo, dout, lddo, lse, dq, lddq, add, klens, H, G, Tq, Tk, causal, scale);
+                     ldo, dout, lddo, lse, dq, lddq, add, klens, rope, inter, H, G, Tq, Tk, causal, scale);
+}
+
+template <typename T, bool EXT, bool ROPE>
+void launch_dkv(const T* q, long ldq, const T* k, long ldk, const T* v, long ldv, const T* o, long ldo, const T* dout,
+                long lddo, const float* lse, T* dk, long lddk, T* dv, long lddv, int addk, int addv, const int* klens,
+                const float* rope, int inter, int B, int H, int KH, int dh, int Tq, int Tk, int causal, float scale,
+                hipStream_t s) {
+  auto kern = dh == 32 ? fm_attn_dkv<T, 32, EXT, ROPE> : dh == 64 ? fm_attn_dkv<T, 64, EXT, ROPE> : fm_attn_dkv<T, 128, EXT, ROPE>;
+  hipLaunchKernelGGL(kern, dim3((Tk + 127) / 128, KH, B), dim3(256), attn_lds<T>(dh) + 2 * Cfg<T>::KT * sizeof(float), s, q,
+                     ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, dk, lddk, dv, lddv, addk, addv, klens, rope, inter, H,
+                     H / KH, Tq, Tk, causal, scale);
+}
+
+// the instantiation a problem runs: lengths or grouped heads (ext) pick the block sharing gs
+template <typename T, bool ROPE> auto pick_fwd(bool ext, int gs) {
+  return !ext      ? launch_fwd<T, 1, false, ROPE>
+         : gs == 4 ? launch_fwd<T, 4, true, ROPE>
+         : gs == 2 ? launch_fwd<T, 2, true, ROPE>
+                   : launch_fwd<T, 1, true, ROPE>;
+}
+template <typename T, bool ROPE> auto pick_dq(bool ext, int gs) {
+  return !ext      ? launch_dq<T, 1, false, ROPE>
+         : gs == 4 ? launch_dq<T, 4, true, ROPE>
+         : gs == 2 ? launch_dq<T, 2, true, ROPE>
+                   : launch_dq<T, 1, true, ROPE>;
 }
 
 template <typename T>
 int attn_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo, float* lse, int B,
-             int H, int KH, int dh, int Tq, int Tk, const int* klens, int causal, float scale, hipStream_t s) {
-  if (int st = attn_status<T>(B, H, KH, dh, Tq, Tk, causal, {q, k, v, o}, {ldq, ldo}, {ldk, ldv})) return st;
+             int H, int KH, int dh, int Tq, int Tk, const int* klens, int causal, float scale, const float* rope, int inter,
+             hipStream_t s) {
+  if (int st = attn_status<T>(B, H, KH, dh, Tq, Tk, causal, {q, k, v, o, rope}, {ldq, ldo}, {ldk, ldv})) return st;
   const int G = H / KH, gs = group_share(G);
-  auto run = !(klens || G > 1) ? launch_fwd<T, 1, false>
-             : gs == 4         ? launch_fwd<T, 4, true>
-             : gs == 2         ? launch_fwd<T, 2, true>
-                               : launch_fwd<T, 1, true>;
-  run((const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (T*)o, ldo, lse, klens, B, H, G, dh, Tq, Tk, causal, scale, s);
+  const bool ext = klens != nullptr || G > 1;
+  auto run = rope ? pick_fwd<T, true>(ext, gs) : pick_fwd<T, false>(ext, gs);
+  run((const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (T*)o, ldo, lse, klens, rope, inter, B, H, G, dh, Tq, Tk, causal,
+      scale, s);
   return 0;
 }
 
@@ -554,28 +765,23 @@ template <typename T>
 int attn_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* o, long ldo,
              const void* dout, long lddo, const float* lse, void* dq, long lddq, void* dk, long lddk, void* dv, long lddv,
              int acc_mask, int B, int H, int KH, int dh, int Tq, int Tk, const int* klens, int causal, float scale,
-             hipStream_t s) {
+             const float* rope, int inter, hipStream_t s) {
   const long need = (long)H * dh;    // a gradient that is absent has no stride to check
-  if (int st = attn_status<T>(B, H, KH, dh, Tq, Tk, causal, {q, k, v, o, dout, dq, dk, dv},
+  if (int st = attn_status<T>(B, H, KH, dh, Tq, Tk, causal, {q, k, v, o, dout, dq, dk, dv, rope},
                               {ldq, ldo, lddo, dq ? lddq : need}, {ldk, ldv, dk ? lddk : need, dv ? lddv : need}))
     return st;
   const int G = H / KH, gs = group_share(G);
   const bool ext = klens != nullptr || G > 1;
   if (dq != nullptr) {
-    auto run = !ext    ? launch_dq<T, 1, false>
-               : gs == 4 ? launch_dq<T, 4, true>
-               : gs == 2 ? launch_dq<T, 2, true>
-                         : launch_dq<T, 1, true>;
+    auto run = rope ? pick_dq<T, true>(ext, gs) : pick_dq<T, false>(ext, gs);
     run((const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (const T*)o, ldo, (const T*)dout, lddo, lse, (T*)dq, lddq,
-        acc_mask & 1, klens, B, H, G, dh, Tq, Tk, causal, scale, s);
+        acc_mask & 1, klens, rope, inter, B, H, G, dh, Tq, Tk, causal, scale, s);
   }
   if (dk != nullptr || dv != nullptr) {
-    auto kern = dh == 32 ? fm_attn_dkv<T, 32, true> : dh == 64 ? fm_attn_dkv<T, 64, true> : fm_attn_dkv<T, 128, true>;
-    if (!ext) kern = dh == 32 ? fm_attn_dkv<T, 32, false> : dh == 64 ? fm_attn_dkv<T, 64, false> : fm_attn_dkv<T, 128, false>;
-    hipLaunchKernelGGL(kern, dim3((Tk + 127) / 128, KH, B), dim3(256), attn_lds<T>(dh) + 2 * Cfg<T>::KT * sizeof(float), s,
-                       (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (const T*)o, ldo, (const T*)dout, lddo, lse,
-                       (T*)dk, lddk, (T*)dv, lddv, (acc_mask >> 1) & 1, (acc_mask >> 2) & 1, klens, H, G, Tq, Tk, causal,
-                       scale);
+    auto run = rope ? (ext ? launch_dkv<T, true, true> : launch_dkv<T, false, true>)
+                    : (ext ? launch_dkv<T, true, false> : launch_dkv<T, false, false>);
+    run((const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, (const T*)o, ldo, (const T*)dout, lddo, lse, (T*)dk, lddk,
+        (T*)dv, lddv, (acc_mask >> 1) & 1, (acc_mask >> 2) & 1, klens, rope, inter, B, H, KH, dh, Tq, Tk, causal, scale, s);
   }
   return 0;
 }
@@ -594,28 +800,33 @@ extern "C" void fm_attention_error(int status, const char** msg) {
 
 extern "C" int fm_attention_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo,
                                 float* lse, int B, int H, int KH, int dh, int Tq, int Tk, const int* key_lengths, int causal,
-                                float scale, hipStream_t s) {
-  return attn_fwd<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, KH, dh, Tq, Tk, key_lengths, causal, scale, s);
+                                float scale, const float* rope, int rope_interleaved, hipStream_t s) {
+  return attn_fwd<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, KH, dh, Tq, Tk, key_lengths, causal, scale, rope,
+                          rope_interleaved, s);
 }
 
 extern "C" int fm_attention_fwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
                                     long ldo, float* lse, int B, int H, int KH, int dh, int Tq, int Tk,
-                                    const int* key_lengths, int causal, float scale, hipStream_t s) {
-  return attn_fwd<float>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, KH, dh, Tq, Tk, key_lengths, causal, scale, s);
+                                    const int* key_lengths, int causal, float scale, const float* rope,
+                                    int rope_interleaved, hipStream_t s) {
+  return attn_fwd<float>(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, KH, dh, Tq, Tk, key_lengths, causal, scale, rope,
+                         rope_interleaved, s);
 }
 
 extern "C" int fm_attention_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* o,
                                 long ldo, const void* dout, long lddo, const float* lse, void* dq, long lddq, void* dk,
                                 long lddk, void* dv, long lddv, int acc_mask, int B, int H, int KH, int dh, int Tq, int Tk,
-                                const int* key_lengths, int causal, float scale, hipStream_t s) {
+                                const int* key_lengths, int causal, float scale, const float* rope, int rope_interleaved,
+                                hipStream_t s) {
   return attn_bwd<bf16_t>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, acc_mask, B, H, KH,
-                          dh, Tq, Tk, key_lengths, causal, scale, s);
+                          dh, Tq, Tk, key_lengths, causal, scale, rope, rope_interleaved, s);
 }
 
 extern "C" int fm_attention_bwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv,
                                     const float* o, long ldo, const float* dout, long lddo, const float* lse, float* dq,
                                     long lddq, float* dk, long lddk, float* dv, long lddv, int acc_mask, int B, int H, int KH,
-                                    int dh, int Tq, int Tk, const int* key_lengths, int causal, float scale, hipStream_t s) {
+                                    int dh, int Tq, int Tk, const int* key_lengths, int causal, float scale, const float* rope,
+                                    int rope_interleaved, hipStream_t s) {
   return attn_bwd<float>(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, lse, dq, lddq, dk, lddk, dv, lddv, acc_mask, B, H, KH,
-                         dh, Tq, Tk, key_lengths, causal, scale, s);
+                         dh, Tq, Tk, key_lengths, causal, scale, rope, rope_interleaved, s);
 }

@@ -120,23 +120,26 @@ int fm_dot_interaction_wide_bwd(const void* const* z, int F, long ldz, const voi
 // b takes part iff j < clamp(key_lengths[b], 0, Tk); it is read by the kernels only, so a captured launch
 // replays with whatever the buffer then holds.  Every launcher returns 0, or a status that
 // fm_attention_error() names and launches nothing.  The backward takes null for an absent gradient;
-// acc_mask bit 0 / 1 / 2: add to dq / dk / dv instead of overwriting.
+// acc_mask bit 0 / 1 / 2: add to dq / dk / dv instead of overwriting.  rope: null, or the rotary table, fp32
+// [>= max(Tq, Tk)][dh] on the device, row t = cos(t w_i), i < dh / 2, then sin(t w_i): q and k rows are rotated by
+// their row index on the way in, dq and dk rotated back on the way out, in column pairs (i, i + dh / 2), or
+// (2i, 2i + 1) when rope_interleaved.
 enum { FM_ATTN_HEAD_DIM = 1, FM_ATTN_SHAPE = 2, FM_ATTN_ALIGN = 3 };
 void fm_attention_error(int status, const char** msg);   // *msg: static text naming the status
 int fm_attention_fwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, void* o, long ldo,
                      float* lse, int B, int H, int KH, int dh, int Tq, int Tk, const int* key_lengths, int causal,
-                     float scale, hipStream_t s);
+                     float scale, const float* rope, int rope_interleaved, hipStream_t s);
 int fm_attention_fwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o, long ldo,
                          float* lse, int B, int H, int KH, int dh, int Tq, int Tk, const int* key_lengths, int causal,
-                         float scale, hipStream_t s);
+                         float scale, const float* rope, int rope_interleaved, hipStream_t s);
 int fm_attention_bwd(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* o, long ldo,
                      const void* dout, long lddo, const float* lse, void* dq, long lddq, void* dk, long lddk, void* dv,
                      long lddv, int acc_mask, int B, int H, int KH, int dh, int Tq, int Tk, const int* key_lengths,
-                     int causal, float scale, hipStream_t s);
+                     int causal, float scale, const float* rope, int rope_interleaved, hipStream_t s);
 int fm_attention_bwd_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* o,
                          long ldo, const float* dout, long lddo, const float* lse, float* dq, long lddq, float* dk,
                          long lddk, float* dv, long lddv, int acc_mask, int B, int H, int KH, int dh, int Tq, int Tk,
-                         const int* key_lengths, int causal, float scale, hipStream_t s);
+                         const int* key_lengths, int causal, float scale, const float* rope, int rope_interleaved, hipStream_t s);
 
 // layernorm.hip: LayerNorm / RMSNorm (rms) over the last dim of [R, D] operands given as base + row
 // stride in elements, s = x + r with r optional.  gamma / beta fp32 [D] or null; stats fp32 [R, 2]

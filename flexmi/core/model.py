@@ -304,17 +304,25 @@ class FFModel:
         t = self.dense(v, D, ActiMode.AC_MODE_NONE, True, None, uinit, bias_initializer or ZeroInitializer(), pre("u"))
         return self.cross_combine(x0, t, None if x is x0 else x, name)
 
-    def attention(self, q, k, v, heads, causal=False, scale=None, name=None, kv_heads=None, key_lengths=None):
+    def attention(self, q, k, v, heads, causal=False, scale=None, name=None, kv_heads=None, key_lengths=None,
+                  rope_base=None, rope_interleaved=False):
         """Fused attention core ``softmax(scale q k^T + mask) v`` per head on ``[B, T, heads * dh]``
         tensors (:class:`flexmi.ops.attention.Attention`); ``scale`` defaults to ``1 / sqrt(dh)``,
         ``causal`` needs ``Tq == Tk``.  The three inputs must be three tensors.  ``kv_heads`` (default
         ``heads``, must divide it): ``k`` / ``v`` are ``[B, Tk, kv_heads * dh]`` and each of their heads
         serves ``heads // kv_heads`` query heads.  ``key_lengths``: an int32 tensor ``[B, 1]``, key ``j``
-        of sample ``b`` is visible iff ``j < key_lengths[b]`` (clamped into ``[0, Tk]``)."""
-        return self._add(Attention(self, q, k, v, heads, causal, scale, name, kv_heads, key_lengths)).outputs[0]
+        of sample ``b`` is visible iff ``j < key_lengths[b]`` (clamped into ``[0, Tk]``).  ``rope_base`` (rotary
+        position embedding, ``None``: none): row ``t`` of ``q`` and of ``k`` is rotated per head by ``t *
+        rope_base ** (-2 i / dh)`` before the scores are formed, in column pairs ``(i, i + dh / 2)``, or ``(2 i,
+        2 i + 1)`` with ``rope_interleaved``; ``dh`` must be even and the base positive.  Not provided: partial
+        rotary (``rotary_dim < dh``), per-sample or offset positions, frequency scaling (NTK / YaRN), and the
+        Keras / torch.fx / ONNX / C surfaces and the native engine."""
+        return self._add(Attention(self, q, k, v, heads, causal, scale, name, kv_heads, key_lengths, rope_base,
+                                   rope_interleaved)).outputs[0]
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, bias=True, causal=False,
-                            kernel_initializer=None, name=None, fp8=None, num_kv_heads=None, key_lengths=None):
+                            kernel_initializer=None, name=None, fp8=None, num_kv_heads=None, key_lengths=None,
+                            rope_base=None, rope_interleaved=False):
         """Multi-head attention on ``query [B, Tq, *]``, ``key`` / ``value [B, Tk, *]``: four ordinary
         Linear ops ``<name>_q/_k/_v/_o`` (no activation, Glorot-uniform kernels as :meth:`dense`, zero
         bias) with the fused :meth:`attention` between them; ``kdim`` / ``vdim`` are checked against
@@ -322,6 +330,8 @@ class FFModel:
         self-attention: the projections make three tensors of it.  ``num_kv_heads`` (grouped-query
         attention): ``<name>_k`` / ``<name>_v`` are ``num_kv_heads * embed_dim // num_heads`` wide;
         ``key_lengths`` (int32 ``[B, 1]``) is ``key_padding_mask`` given as the count of real keys.
+        ``rope_base`` / ``rope_interleaved`` go to :meth:`attention` (rotary position embedding of the projected
+        ``q`` and ``k``; what is not provided is listed there).
 
         Weights map to ``torch.nn.MultiheadAttention(embed_dim, num_heads, batch_first=True)`` with
         ``E = embed_dim``: ``<name>_q.weight = in_proj_weight[0:E]``, ``<name>_k.weight =
@@ -342,7 +352,8 @@ class FFModel:
                                                         kernel_initializer, None, pre(s), fp8)
         kv_width = embed_dim // num_heads * kv_heads
         q, k, v = proj(query, "q"), proj(key, "k", kv_width), proj(value, "v", kv_width)
-        return proj(self.attention(q, k, v, num_heads, causal, None, name, kv_heads, key_lengths), "o")
+        return proj(self.attention(q, k, v, num_heads, causal, None, name, kv_heads, key_lengths, rope_base,
+                                   rope_interleaved), "o")
 
     def layer_norm(self, x, residual=None, eps=1e-5, elementwise_affine=True, rms=False, name=None):
         """LayerNorm over the last dim of ``x [..., D]`` (:class:`flexmi.ops.norm.LayerNorm`), of ``x +
@@ -352,7 +363,8 @@ class FFModel:
         return self._add(LayerNorm(self, x, residual, eps, elementwise_affine, rms, name)).outputs[0]
 
     def transformer_encoder_layer(self, x, num_heads, dim_feedforward, causal=False, norm_first=False, name=None,
-                                  attention_bias=True, fp8=None, num_kv_heads=None, key_lengths=None):
+                                  attention_bias=True, fp8=None, num_kv_heads=None, key_lengths=None, rope_base=None,
+                                  rope_interleaved=False):
         """One transformer encoder layer on ``x [B, T, E]`` without dropout: self-attention
         (:meth:`multihead_attention`, ``<name>_attn``), a feed-forward of two :meth:`dense` ops
         ``<name>_ff1`` (ReLU, ``dim_feedforward`` wide) and ``<name>_ff2``, and two :meth:`layer_norm` ops
@@ -360,7 +372,8 @@ class FFModel:
         layer_norm(attn(x), residual=x)``, ``out = layer_norm(ffn(h), residual=h)``.  ``norm_first``:
         ``h = x + attn(layer_norm(x))``, ``out = h + ffn(layer_norm(h))`` with the plain :meth:`add`.
         ``attention_bias=False`` builds the four attention projections without bias; ``fp8`` goes to all six
-        :meth:`dense` calls; ``num_kv_heads`` and ``key_lengths`` go to :meth:`multihead_attention`.
+        :meth:`dense` calls; ``num_kv_heads``, ``key_lengths``, ``rope_base`` and ``rope_interleaved`` go to
+        :meth:`multihead_attention` (rotary positions: see :meth:`attention`, and what it does not provide).
 
         Weights map to ``torch.nn.TransformerEncoderLayer(E, num_heads, dim_feedforward, dropout=0,
         batch_first=True, norm_first=norm_first)``: ``<name>_attn_q/_k/_v/_o`` to ``self_attn`` as
@@ -371,7 +384,8 @@ class FFModel:
         pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
         attn = lambda t: self.multihead_attention(t, t, t, E, num_heads, bias=attention_bias, causal=causal,  # noqa: E731
                                                   name=pre("attn"), fp8=fp8, num_kv_heads=num_kv_heads,
-                                                  key_lengths=key_lengths)
+                                                  key_lengths=key_lengths, rope_base=rope_base,
+                                                  rope_interleaved=rope_interleaved)
         ffn = lambda t: self.dense(self.dense(t, dim_feedforward, ActiMode.AC_MODE_RELU, name=pre("ff1"), fp8=fp8), E,  # noqa: E731
                                    name=pre("ff2"), fp8=fp8)
         if norm_first:

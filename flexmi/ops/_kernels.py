@@ -379,23 +379,30 @@ def dot_interaction_backward(inputs, dy, in_grads, accs, self_inter, act0=10):
 
 
 # ------------------------------------------------------------------ fused attention
-def attention_forward(q, k, v, out, lse, heads, causal, scale, kv_heads=None, key_lengths=None):
+def attention_forward(q, k, v, out, lse, heads, causal, scale, kv_heads=None, key_lengths=None, rope=None,
+                      rope_interleaved=False):
     """``out = softmax(scale q k^T + mask) v`` per head on [B, T, heads * dh] operands (column slices
     of wider buffers allowed) and the per-row log-sum-exp ``lse`` [B, heads, Tq] fp32
     (csrc/kernels/attention.hip).  ``kv_heads`` (default ``heads``, must divide it): ``k`` / ``v`` are
     [B, Tk, kv_heads * dh] and query head ``h`` reads KV head ``h // (heads // kv_heads)``.
     ``key_lengths``: int32 device tensor of B elements, key ``j`` of sample ``b`` is visible iff
-    ``j < clamp(key_lengths[b], 0, Tk)``; a row without a visible key gets output 0."""
-    C().attn_fwd(q, k, v, out, lse, int(heads), bool(causal), float(scale), int(kv_heads or heads), key_lengths)
+    ``j < clamp(key_lengths[b], 0, Tk)``; a row without a visible key gets output 0.  ``rope``: the rotary
+    table of :func:`flexmi.ops.attention.rope_table` on the device, fp32 [>= max(Tq, Tk), dh]; row ``t`` of
+    ``q`` and of ``k`` is rotated by position ``t`` per head before the scores are formed, in column pairs
+    ``(i, i + dh/2)``, or ``(2i, 2i + 1)`` when ``rope_interleaved``."""
+    C().attn_fwd(q, k, v, out, lse, int(heads), bool(causal), float(scale), int(kv_heads or heads), key_lengths, rope,
+                 bool(rope_interleaved))
 
 
-def attention_backward(q, k, v, out, dout, lse, dq, dk, dv, accs, heads, causal, scale, kv_heads=None, key_lengths=None):
+def attention_backward(q, k, v, out, dout, lse, dq, dk, dv, accs, heads, causal, scale, kv_heads=None, key_lengths=None,
+                       rope=None, rope_interleaved=False):
     """The true gradients of :func:`attention_forward`; a ``None`` gradient is not computed, ``accs``
     are the three accumulate flags.  ``dk`` / ``dv`` have the shape of ``k`` / ``v`` (summed over a
-    group's query heads); rows at or past a sample's length get 0, or keep their value under accumulate."""
+    group's query heads); rows at or past a sample's length get 0, or keep their value under accumulate.
+    With ``rope``, ``dq`` and ``dk`` are the gradients of the unrotated ``q`` and ``k``."""
     mask = sum(1 << i for i, (g, a) in enumerate(zip((dq, dk, dv), accs)) if a and g is not None)
     C().attn_bwd(q, k, v, out, dout, lse, dq, dk, dv, mask, int(heads), bool(causal), float(scale), int(kv_heads or heads),
-                 key_lengths)
+                 key_lengths, rope, bool(rope_interleaved))
 
 
 # ------------------------------------------------------------------ LayerNorm / RMSNorm

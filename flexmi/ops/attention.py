@@ -20,6 +20,20 @@ lengths are read on the device only, so a captured step replays with whatever it
 The backward is the true gradient of all three inputs (the framework's ``Softmax.backward`` is the
 identity: it only ever sat in front of the cross-entropy loss).  The CPU path is the explicit
 formula in fp32, its backward written out; padded key rows are selected away, never multiplied by 0.
+
+``rope_base`` (rotary position embedding, default ``None``: no rotation, the op as it was): with a base
+``theta`` (10000.0 is the usual one) row ``t`` of ``q`` and row ``t`` of ``k`` are rotated per head by the angles
+``t * theta ** (-2 i / dh)``, ``i`` in ``[0, dh / 2)``, before the scores are formed; ``v`` and the output are
+untouched.  The default pairs columns ``(i, i + dh / 2)`` (half-split: GPT-NeoX, Hugging Face Llama),
+``rope_interleaved`` pairs ``(2 i, 2 i + 1)`` (GPT-J, RoFormer).  Positions are row indices, with ``causal``,
+``kv_heads`` and ``key_lengths`` alike (right for right-padded batches); a KV head is rotated once however
+many query heads read it.  ``dq`` / ``dk`` are the true gradients: those of the rotated rows, rotated back by
+the transpose.  The cos / sin table (:func:`rope_table`) is computed once in float64 on the host, rounded to
+fp32 and kept with the op; both backends read it, the HIP kernels from a device copy made at
+``init_layers()``, rotating ``q`` / ``k`` on their way into the matrix instructions and ``dq`` / ``dk`` on their
+way out of the accumulators: no extra pass over memory.  Not provided: partial rotary (``rotary_dim < dh``),
+per-sample or offset positions, frequency scaling (NTK / YaRN), and the Keras / torch.fx / ONNX / C surfaces
+and the native engine.
 """
 from __future__ import annotations
 
@@ -34,12 +48,33 @@ from .base import Op, OpCtx, store
 from . import _kernels as K
 
 
+def rope_table(positions, dh, base):
+    """fp32 ``[positions, dh]``: row ``t`` holds ``cos(t w_i)`` then ``sin(t w_i)``, ``w_i = base ** (-2 i / dh)``,
+    ``i < dh / 2``, computed in float64 and rounded once.  A row is what one position needs, and its 16-byte
+    pieces are the frequencies of the 16-byte chunks the kernels load of ``q`` and ``k``."""
+    w = float(base) ** (-torch.arange(0, dh, 2, dtype=torch.float64) / dh)
+    ang = torch.arange(positions, dtype=torch.float64)[:, None] * w[None, :]
+    return torch.cat((ang.cos(), ang.sin()), 1).float()
+
+
+def rope_rotate(x, table, interleaved, transpose=False):
+    """``x [..., T, dh]`` with row ``t`` rotated by row ``t`` of ``table``; ``transpose``: by the inverse."""
+    half = x.shape[-1] // 2
+    c, s = table[:x.shape[-2], :half].to(x.dtype), table[:x.shape[-2], half:].to(x.dtype)
+    if transpose:
+        s = -s
+    lo, hi = (x[..., 0::2], x[..., 1::2]) if interleaved else (x[..., :half], x[..., half:])
+    lo, hi = lo * c - hi * s, hi * c + lo * s
+    return torch.stack((lo, hi), -1).flatten(-2) if interleaved else torch.cat((lo, hi), -1)
+
+
 class Attention(Op):
     op_type = OperatorType.OP_ATTENTION
     name_prefix = "Attention"
     HIP_HEAD_DIMS = (32, 64, 128)
 
-    def __init__(self, model, q, k, v, heads, causal=False, scale=None, name=None, kv_heads=None, key_lengths=None):
+    def __init__(self, model, q, k, v, heads, causal=False, scale=None, name=None, kv_heads=None, key_lengths=None,
+                 rope_base=None, rope_interleaved=False):
         super().__init__(model, [q, k, v] + ([] if key_lengths is None else [key_lengths]), name)
         heads = int(heads)
         kv_heads = heads if kv_heads is None else int(kv_heads)
@@ -60,6 +95,14 @@ class Attention(Op):
             raise ValueError(f"Attention: key_lengths must be an int32 tensor [{B}, 1], got {key_lengths.data_type.name} "
                              f"{tuple(key_lengths.dims)}")
         self.heads, self.kv_heads, self.dh, self.causal = heads, kv_heads, E // heads, bool(causal)
+        if rope_base is not None and self.dh % 2 != 0:
+            raise ValueError(f"Attention: rope_base needs an even head dimension, got {self.dh}")
+        if rope_base is not None and not float(rope_base) > 0:
+            raise ValueError(f"Attention: rope_base must be positive, got {rope_base}")
+        self.rope_base = None if rope_base is None else float(rope_base)
+        self.rope_interleaved = bool(rope_interleaved)
+        # positions are row indices: the table depends on nothing a sample split changes
+        self.rope = None if rope_base is None else rope_table(max(Tq, k.dims[1]), self.dh, self.rope_base)
         self.has_lengths = key_lengths is not None
         self.scale = float(scale) if scale is not None else 1.0 / math.sqrt(self.dh)
         if self.name is None:
@@ -73,6 +116,15 @@ class Attention(Op):
                              f"{self.HIP_HEAD_DIMS}; the CPU backend has no limit")
         if self.heads > 65535:
             raise ValueError(f"Attention '{self.name}' has {self.heads} heads: the HIP kernels take at most 65535")
+
+    def prepare(self, ctx):
+        """The rotary table at its fixed device address before any step can be captured."""
+        if self.rope is not None and ctx.inputs and ctx.inputs[0] is not None:
+            ctx.saved["rope"] = self.rope.to(ctx.inputs[0].device)
+
+    def _rope(self, x, transpose=False):
+        """fp32 heads [B, n, T, dh] rotated by their row index (``transpose``: gradients rotated back)."""
+        return x if self.rope is None else rope_rotate(x, self.rope.to(x.device), self.rope_interleaved, transpose)
 
     def splittable_dims(self):
         return {0}
@@ -100,7 +152,7 @@ class Attention(Op):
             k, v = torch.where(live[:, :, None], k, zero), torch.where(live[:, :, None], v, zero)
             vis = live[:, None, None, :] if vis is None else vis & live[:, None, None, :]
         G = self.heads // self.kv_heads
-        kh, vh = self._heads(k, self.kv_heads), self._heads(v, self.kv_heads)
+        kh, vh = self._rope(self._heads(k, self.kv_heads)), self._heads(v, self.kv_heads)   # a KV head rotated once
         if G > 1:
             kh, vh = kh.repeat_interleave(G, 1), vh.repeat_interleave(G, 1)
         return kh, vh, vis
@@ -123,10 +175,10 @@ class Attention(Op):
                 lse = ctx.saved["lse"] = torch.empty(q.shape[0], self.heads, q.shape[1], dtype=torch.float32,
                                                      device=q.device)
             K.attention_forward(q, k, v, y, lse, self.heads, self.causal, self.scale, self.kv_heads,
-                                ctx.inputs[3] if self.has_lengths else None)
+                                ctx.inputs[3] if self.has_lengths else None, ctx.saved.get("rope"), self.rope_interleaved)
             return
         kh, vh, vis = self._kv(ctx)
-        o = torch.matmul(self._probs(self._heads(q, self.heads), kh, vis), vh)
+        o = torch.matmul(self._probs(self._rope(self._heads(q, self.heads)), kh, vis), vh)
         y.copy_(o.transpose(1, 2).reshape(y.shape))
 
     def backward(self, ctx: OpCtx):
@@ -138,9 +190,10 @@ class Attention(Op):
             return
         if ctx.hip:
             K.attention_backward(q, k, v, ctx.outputs[0], dy, ctx.saved["lse"], g[0], g[1], g[2], acc, self.heads,
-                                 self.causal, self.scale, self.kv_heads, ctx.inputs[3] if self.has_lengths else None)
+                                 self.causal, self.scale, self.kv_heads, ctx.inputs[3] if self.has_lengths else None,
+                                 ctx.saved.get("rope"), self.rope_interleaved)
             return
-        qh, do = self._heads(q, self.heads), self._heads(dy, self.heads)
+        qh, do = self._rope(self._heads(q, self.heads)), self._heads(dy, self.heads)
         kh, vh, vis = self._kv(ctx)
         p = self._probs(qh, kh, vis)
         dp = torch.matmul(do, vh.transpose(-1, -2))
@@ -149,9 +202,9 @@ class Attention(Op):
         # [B, heads, Tk, dh] -> the sum over each KV head's group
         group = lambda t: t.reshape(t.shape[0], self.kv_heads, -1, *t.shape[2:]).sum(2)   # noqa: E731
         if g[0] is not None:
-            store(g[0], back(torch.matmul(ds, kh)), acc[0])
+            store(g[0], back(self._rope(torch.matmul(ds, kh), True)), acc[0])
         if g[1] is not None:
-            store(g[1], back(group(torch.matmul(ds.transpose(-1, -2), qh))), acc[1])
+            store(g[1], back(self._rope(group(torch.matmul(ds.transpose(-1, -2), qh)), True)), acc[1])
         if g[2] is not None:
             store(g[2], back(group(torch.matmul(p.transpose(-1, -2), do))), acc[2])
 

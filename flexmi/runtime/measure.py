@@ -34,7 +34,8 @@ def _make_clone(op, m, in_shapes, out_shapes):
         m.cross_combine(ins[0], ins[1], ins[2] if len(ins) > 2 else None)
     elif t == OperatorType.OP_ATTENTION:
         m.attention(ins[0], ins[1], ins[2], op.heads, op.causal, op.scale, kv_heads=op.kv_heads,
-                    key_lengths=ins[3] if op.has_lengths else None)
+                    key_lengths=ins[3] if op.has_lengths else None, rope_base=op.rope_base,
+                    rope_interleaved=op.rope_interleaved)
     elif t == OperatorType.OP_LAYERNORM:
         m.layer_norm(ins[0], ins[1] if len(ins) > 1 else None, op.eps, op.affine, op.rms)
     elif t == OperatorType.OP_CONCAT:

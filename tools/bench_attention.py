@@ -3,7 +3,7 @@
 forward composed from the project's ``bmm`` + ``softmax`` + ``bmm``.
 
     python tools/bench_attention.py [--out profiles/attention.txt] [--rounds 5] [--reps 4] [--quick]
-                                    [--kv-heads N] [--mean-length M]
+                                    [--kv-heads N] [--mean-length M] [--rope half|interleaved]
 
 ``B = 32, heads = 8, dh in {64, 128}, T in {512, 2048}``, causal and not, bf16 and fp32.  Each
 variant's ``reps`` back-to-back calls are captured into one hipGraph; the variants of one shape are
@@ -18,6 +18,8 @@ identity, which is why the fused op exists.
 ``--mean-length M`` gives every sample a key length drawn uniformly from ``M - w .. M + w``, ``w = min(M,
 T - M)``, with a fixed seed (a ``T`` below ``M`` is skipped).  Either drops the composition, which can do neither, and TF/s stays over
 the flops of the full-length problem, so that a time saved shows as a higher figure.
+``--rope half|interleaved`` rotates ``q`` and ``k`` in the kernels (rotary position embedding, base 10000); it drops
+the composition as well, and TF/s stays over the flops of the products alone.
 """
 from __future__ import annotations
 
@@ -32,7 +34,7 @@ sys.path.insert(0, ROOT)
 from tools.bench_cross import capture, replay_us  # noqa: E402
 
 
-def variants(B, H, dh, T, causal, dtype, dev, kv_heads=None, mean_length=None):
+def variants(B, H, dh, T, causal, dtype, dev, kv_heads=None, mean_length=None, rope=None):
     import torch
     from flexmi.ops import _kernels as K
     g = torch.Generator(device=dev).manual_seed(0)
@@ -44,16 +46,22 @@ def variants(B, H, dh, T, causal, dtype, dev, kv_heads=None, mean_length=None):
         w = min(mean_length, T - mean_length)
         lens = torch.randint(mean_length - w, mean_length + w + 1, (B, 1), generator=g, device=dev).int()
     lse = torch.empty(B, H, T, device=dev)
+    tab = None
+    if rope is not None:
+        from flexmi.ops.attention import rope_table
+        tab = rope_table(T, dh, 10000.0).to(dev)
+    inter = rope == "interleaved"
     scale = dh ** -0.5
 
     def fused_fwd():
-        K.attention_forward(q, k, v, out, lse, H, causal, scale, KH, lens)
+        K.attention_forward(q, k, v, out, lse, H, causal, scale, KH, lens, tab, inter)
 
     def fused_bwd():
-        K.attention_backward(q, k, v, out, dout, lse, dq, dk, dv, (False, False, False), H, causal, scale, KH, lens)
+        K.attention_backward(q, k, v, out, dout, lse, dq, dk, dv, (False, False, False), H, causal, scale, KH, lens, tab,
+                             inter)
 
     fl = 4.0 * B * H * T * T * dh * (0.5 if causal else 1.0)
-    if KH != H or lens is not None:
+    if KH != H or lens is not None or tab is not None:
         return [("fwd", "fused", fused_fwd, fl), ("bwd", "fused", fused_bwd, 2.5 * fl)]
     hm = lambda t: t.reshape(B, T, H, dh).transpose(1, 2).reshape(B * H, T, dh).contiguous()   # noqa: E731
     qh, kh, vh = hm(q * scale), hm(k), hm(v)
@@ -77,23 +85,25 @@ def main():
     ap.add_argument("--quick", action="store_true", help="T = 512 only")
     ap.add_argument("--kv-heads", type=int, default=None, help="heads of k / v (default: all 8)")
     ap.add_argument("--mean-length", type=int, default=None, help="mean of the per-sample key lengths (default: none given)")
+    ap.add_argument("--rope", choices=("half", "interleaved"), default=None, help="rotary position embedding of q and k")
+    ap.add_argument("--long", action="store_true", help="T = 2048 only")
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "bench_attention needs a GPU"
     dev = torch.device("cuda", 0)
     B, H = 32, 8
     lines = [f"# tools/bench_attention.py on {torch.cuda.get_device_name(0)}: B={B} heads={H} kv_heads={a.kv_heads or H} "
-             f"mean_length={a.mean_length}, {a.reps} calls per hipGraph, "
+             f"mean_length={a.mean_length} rope={a.rope}, {a.reps} calls per hipGraph, "
              f"{a.rounds} alternating replays per variant; us per call: median [min .. max]; TF/s over algorithmic flops",
              f"{'dh':>4}{'T':>6}{'causal':>7} {'dtype':<6}{'pass':<5}{'variant':<10}{'us':>10}{'min':>10}{'max':>10}{'TF/s':>8}"
              f"{'fused/composed':>16}"]
     for dh in (64, 128):
-        for T in ((512,) if a.quick else (512, 2048)):
+        for T in ((512,) if a.quick else (2048,) if a.long else (512, 2048)):
             if a.mean_length is not None and a.mean_length > T:
                 continue
             for causal in (False, True):
                 for dtype in (torch.bfloat16, torch.float32):
-                    vs = variants(B, H, dh, T, causal, dtype, dev, a.kv_heads, a.mean_length)
+                    vs = variants(B, H, dh, T, causal, dtype, dev, a.kv_heads, a.mean_length, a.rope)
                     graphs = [capture(fn, a.reps) for _, _, fn, _ in vs]
                     times = [[] for _ in vs]
                     for _ in range(a.rounds):                # alternate the variants within the session
