@@ -996,6 +996,79 @@ void mx_gemm(torch::Tensor A, torch::Tensor sa, int64_t fmt_a, torch::Tensor B, 
                                  is_bf16(Cout) ? 0 : 1, fptr(bias), (int)act, beta ? 1 : 0, (int)M, (int)N, (int)K, cur()));
 }
 
+// ---- gated feed-forward (glu.hip) ----------------------------------------------------------------------
+// an [M, cols] bf16 / fp32 device operand of dtype dt with unit column stride; returns its row stride
+int64_t glu_operand(const char* fn, const torch::Tensor& t, int64_t M, int64_t cols, torch::ScalarType dt, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.size(0) == M && t.size(1) == cols && t.scalar_type() == dt &&
+                  (cols == 0 || t.stride(1) == 1),
+              fn, " ", what, ": [", M, ", ", cols, "] device tensor of the operands' dtype with unit column stride expected");
+  const int64_t ld = M > 1 ? t.stride(0) : cols;
+  TORCH_CHECK(ld >= cols && (M == 0 || extent(t) >= (M - 1) * ld + cols), fn, " ", what, ": row stride of at least the width expected");
+  return ld;
+}
+
+void glu_first(const char* fn, const torch::Tensor& t, int64_t F) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2 && F >= 1 && F <= INT32_MAX / 2 &&
+                  (t.scalar_type() == torch::kBFloat16 || t.scalar_type() == torch::kFloat32),
+              fn, ": 2-d bf16 or fp32 device operands and 1 <= F < 2^30 expected");
+}
+
+// the fused forward would take these operands (shape, strides, alignment)
+bool glu_gemm_eligible(torch::Tensor x, torch::Tensor w, torch::Tensor gu, torch::Tensor h) {
+  if (!(x.is_cuda() && x.dim() == 2 && w.dim() == 2 && h.dim() == 2 && gu.dim() == 2 && x.stride(1) == 1 && h.stride(1) == 1 &&
+        is_bf16(x) && is_bf16(w) && is_bf16(gu) && is_bf16(h) && w.is_contiguous() && gu.is_contiguous()))
+    return false;
+  const int64_t M = x.size(0), H = x.size(1), F = h.size(1);
+  if (w.size(0) != 2 * F || w.size(1) != H || gu.size(0) != M || gu.size(1) != 2 * F || h.size(0) != M || F > INT32_MAX / 2 ||
+      H > INT32_MAX)
+    return false;
+  return fm_glu_gemm_eligible(x.data_ptr(), M > 1 ? x.stride(0) : H, w.data_ptr(), gu.data_ptr(), h.data_ptr(),
+                              M > 1 ? h.stride(0) : F, M, (int)F, (int)H) != 0;
+}
+
+// gu = x w^T (rounded, stored) and h = act(g) * u in one kernel; bf16 only
+void glu_gemm_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor gu, torch::Tensor h, int64_t act) {
+  const int64_t F = h.dim() == 2 ? h.size(1) : 0;
+  glu_first("glu_gemm_fwd", x, F);
+  TORCH_CHECK(is_bf16(x), "glu_gemm_fwd: bf16 operands expected (fp32 takes the composed form)");
+  const int64_t M = x.size(0), H = x.size(1);
+  TORCH_CHECK(H >= 1 && H <= INT32_MAX, "glu_gemm_fwd: bad H");
+  const int64_t ldx = glu_operand("glu_gemm_fwd", x, M, H, torch::kBFloat16, "x");
+  const int64_t ldh = glu_operand("glu_gemm_fwd", h, M, F, torch::kBFloat16, "h");
+  TORCH_CHECK(glu_operand("glu_gemm_fwd", w, 2 * F, H, torch::kBFloat16, "w") == H && w.is_contiguous(),
+              "glu_gemm_fwd w: contiguous [2F, H] expected");
+  TORCH_CHECK(glu_operand("glu_gemm_fwd", gu, M, 2 * F, torch::kBFloat16, "gu") == 2 * F && gu.is_contiguous(),
+              "glu_gemm_fwd gu: contiguous [M, 2F] expected");
+  TORCH_CHECK(fm_glu_gemm_fwd(x.data_ptr(), ldx, w.data_ptr(), gu.data_ptr(), h.data_ptr(), ldh, M, (int)F, (int)H, (int)act,
+                              cur()) == 0,
+              "glu_gemm_fwd: operands outside the fused kernel's contract (F % 4, H % 8, row strides % 8 (x) / % 4 (h), "
+              "16-B aligned bases, activation 0 / 1)");
+}
+
+// h = act(gu[:, :F]) * gu[:, F:]
+void glu_act_fwd(torch::Tensor gu, torch::Tensor h, int64_t act) {
+  const int64_t F = h.dim() == 2 ? h.size(1) : 0;
+  glu_first("glu_act_fwd", h, F);
+  const int64_t M = h.size(0);
+  const int64_t ldgu = glu_operand("glu_act_fwd", gu, M, 2 * F, h.scalar_type(), "gu");
+  const int64_t ldh = glu_operand("glu_act_fwd", h, M, F, h.scalar_type(), "h");
+  TORCH_CHECK(fm_glu_act_fwd(gu.data_ptr(), ldgu, h.data_ptr(), ldh, M, (int)F, (int)act, is_bf16(h), cur()) == 0,
+              "glu_act_fwd: refused (activation 0 / 1, row strides of at least the width)");
+}
+
+// dgu[:, :F] = dh * u * act'(g), dgu[:, F:] = dh * act(g)
+void glu_act_bwd(torch::Tensor dh, torch::Tensor gu, torch::Tensor dgu, int64_t act) {
+  const int64_t F = dh.dim() == 2 ? dh.size(1) : 0;
+  glu_first("glu_act_bwd", dh, F);
+  const int64_t M = dh.size(0);
+  const int64_t lddh = glu_operand("glu_act_bwd", dh, M, F, dh.scalar_type(), "dh");
+  const int64_t ldgu = glu_operand("glu_act_bwd", gu, M, 2 * F, dh.scalar_type(), "gu");
+  const int64_t lddgu = glu_operand("glu_act_bwd", dgu, M, 2 * F, dh.scalar_type(), "dgu");
+  TORCH_CHECK(fm_glu_act_bwd(dh.data_ptr(), lddh, gu.data_ptr(), ldgu, dgu.data_ptr(), lddgu, M, (int)F, (int)act, is_bf16(dh),
+                             cur()) == 0,
+              "glu_act_bwd: refused (activation 0 / 1, row strides of at least the width)");
+}
+
 void sgd(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, c10::optional<torch::Tensor> Wc, torch::Tensor lr,
          double wd, double mom, bool nesterov, bool zero_grad) {
   check_update("sgd", W, G, {V}, Wc, lr);
@@ -1788,6 +1861,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_bwd", &attn_bwd);
   m.def("ln_fwd", &ln_fwd);
   m.def("ln_bwd", &ln_bwd);
+  m.def("glu_gemm_eligible", &glu_gemm_eligible);
+  m.def("glu_gemm_fwd", &glu_gemm_fwd);
+  m.def("glu_act_fwd", &glu_act_fwd);
+  m.def("glu_act_bwd", &glu_act_bwd);
   m.def("mx_quant", &mx_quant);
   m.def("mx_quant_dact", &mx_quant_dact);
   m.def("mx_gemm", &mx_gemm);

@@ -55,6 +55,16 @@ int fm_smallk_dw_launch(const void* dpre, long ldd, const void* x, long ldx, flo
                         float* ws, long ws_bytes, float* V, unsigned short* Wc, const float* lr, float wd, float mom,
                         int nesterov, int bf16, hipStream_t s);
 
+// glu.hip: gated feed-forward.  w [2F][H] (gate rows, then up rows) and gu [M][2F] are contiguous; act 0 = SiLU,
+// 1 = exact GELU.  The launchers return 0, or 1 when they refuse the operands (nothing is launched then).
+int fm_glu_gemm_eligible(const void* x, long ldx, const void* w, const void* gu, const void* h, long ldh, long M, int F,
+                         int H);
+int fm_glu_gemm_fwd(const void* x, long ldx, const void* w, void* gu, void* h, long ldh, long M, int F, int H, int act,
+                    hipStream_t stream);
+int fm_glu_act_fwd(const void* gu, long ldgu, void* h, long ldh, long M, int F, int act, int bf16, hipStream_t stream);
+int fm_glu_act_bwd(const void* dh, long lddh, const void* gu, long ldgu, void* dgu, long lddgu, long M, int F, int act,
+                   int bf16, hipStream_t stream);
+
 // embedding.hip
 void fm_embedding_fwd_multi(int n, const float* const* W, const void* const* idx, const int* idx64, void* const* out,
                             const long* ldo, const long* lo, const int* rows, const int* D, const int* bag,

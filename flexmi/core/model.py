@@ -27,6 +27,7 @@ from flexmi.ops.conv import BatchNorm, Conv2D, Pool2D
 from flexmi.ops.cross import CrossCombine
 from flexmi.ops.elementwise import ElementBinary, ElementUnary
 from flexmi.ops.embedding import Embedding
+from flexmi.ops.gated import GatedLinear
 from flexmi.ops.linear import Linear
 from flexmi.ops.linear_mx import LinearMX, mx_eligible
 from flexmi.ops.norm import LayerNorm
@@ -242,6 +243,14 @@ class FFModel:
         self._share(op, shared_op)
         return self._add(op).outputs[0]
 
+    def gated_dense(self, input, out_dim, activation="silu", kernel_initializer=None, name=None):
+        """Gated feed-forward layer ``act(x Wg^T) * (x Wu^T)`` on ``input [..., H]`` -> ``[..., out_dim]``
+        (:class:`flexmi.ops.gated.GatedLinear`): ``activation`` ``"silu"`` is SwiGLU, ``"gelu"`` GeGLU (exact erf
+        form); anything else is a ValueError.  One parameter ``kernel [2 * out_dim, H]`` without bias: rows ``[0,
+        out_dim)`` are Hugging Face Llama's ``gate_proj.weight``, rows ``[out_dim, 2 * out_dim)`` its
+        ``up_proj.weight``.  Each half is initialised as a ``dense(input, out_dim)`` kernel would be."""
+        return self._add(GatedLinear(self, input, out_dim, activation, kernel_initializer, name)).outputs[0]
+
     def concat(self, tensors, axis, name=None):
         return self._add(Concat(self, tensors, axis, name)).outputs[0]
 
@@ -364,7 +373,7 @@ class FFModel:
 
     def transformer_encoder_layer(self, x, num_heads, dim_feedforward, causal=False, norm_first=False, name=None,
                                   attention_bias=True, fp8=None, num_kv_heads=None, key_lengths=None, rope_base=None,
-                                  rope_interleaved=False):
+                                  rope_interleaved=False, ffn="relu", rms_norm=False, ffn_bias=True):
         """One transformer encoder layer on ``x [B, T, E]`` without dropout: self-attention
         (:meth:`multihead_attention`, ``<name>_attn``), a feed-forward of two :meth:`dense` ops
         ``<name>_ff1`` (ReLU, ``dim_feedforward`` wide) and ``<name>_ff2``, and two :meth:`layer_norm` ops
@@ -379,20 +388,39 @@ class FFModel:
         batch_first=True, norm_first=norm_first)``: ``<name>_attn_q/_k/_v/_o`` to ``self_attn`` as
         :meth:`multihead_attention` documents, ``<name>_ff1`` = ``linear1``, ``<name>_ff2`` = ``linear2``
         (kernels [out, in] on both sides), ``<name>_norm1/2.scale`` = ``norm1/2.weight`` and ``.bias`` =
-        ``norm1/2.bias``; ``causal`` corresponds to ``src_mask = generate_square_subsequent_mask(T)``."""
+        ``norm1/2.bias``; ``causal`` corresponds to ``src_mask = generate_square_subsequent_mask(T)``.
+
+        ``ffn="swiglu"`` / ``"geglu"`` builds ``<name>_ff1`` as :meth:`gated_dense` (``dim_feedforward`` wide, SiLU /
+        GELU gate, no bias) instead of the ReLU :meth:`dense`; ``fp8`` then goes to ``<name>_ff2`` only.  Any other
+        string than these and ``"relu"`` is a ValueError.  ``rms_norm=True`` makes both norms RMSNorm;
+        ``ffn_bias=False`` builds the feed-forward :meth:`dense` ops without bias.
+
+        A Hugging Face Llama decoder layer is ``norm_first=True, rms_norm=True, ffn="swiglu", ffn_bias=False,
+        attention_bias=False, causal=True, rope_base=..., num_kv_heads=...``: ``<name>_norm1.scale`` =
+        ``input_layernorm.weight``, ``<name>_norm2.scale`` = ``post_attention_layernorm.weight``,
+        ``<name>_attn_q/_k/_v/_o.weight`` = ``self_attn.q_proj/k_proj/v_proj/o_proj.weight``, rows ``[0, F)`` of
+        ``<name>_ff1.kernel`` = ``mlp.gate_proj.weight`` and rows ``[F, 2F)`` = ``mlp.up_proj.weight`` (``F =
+        dim_feedforward``), ``<name>_ff2.weight`` = ``mlp.down_proj.weight``.  The norms use
+        ``eps = 1e-5``; a model with another ``rms_norm_eps`` is built from the layer's parts."""
+        if ffn not in ("relu", "swiglu", "geglu"):
+            raise ValueError(f"transformer_encoder_layer: ffn {ffn!r}; 'relu', 'swiglu' or 'geglu' expected")
         E = x.dims[-1]
         pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
         attn = lambda t: self.multihead_attention(t, t, t, E, num_heads, bias=attention_bias, causal=causal,  # noqa: E731
                                                   name=pre("attn"), fp8=fp8, num_kv_heads=num_kv_heads,
                                                   key_lengths=key_lengths, rope_base=rope_base,
                                                   rope_interleaved=rope_interleaved)
-        ffn = lambda t: self.dense(self.dense(t, dim_feedforward, ActiMode.AC_MODE_RELU, name=pre("ff1"), fp8=fp8), E,  # noqa: E731
-                                   name=pre("ff2"), fp8=fp8)
+        if ffn == "relu":
+            ff1 = lambda t: self.dense(t, dim_feedforward, ActiMode.AC_MODE_RELU, ffn_bias, name=pre("ff1"), fp8=fp8)  # noqa: E731
+        else:
+            ff1 = lambda t: self.gated_dense(t, dim_feedforward, "silu" if ffn == "swiglu" else "gelu", name=pre("ff1"))  # noqa: E731
+        ffw = lambda t: self.dense(ff1(t), E, use_bias=ffn_bias, name=pre("ff2"), fp8=fp8)  # noqa: E731
+        norm = lambda t, s, residual=None: self.layer_norm(t, residual, rms=rms_norm, name=pre(s))  # noqa: E731
         if norm_first:
-            h = self.add(x, attn(self.layer_norm(x, name=pre("norm1"))))
-            return self.add(h, ffn(self.layer_norm(h, name=pre("norm2"))))
-        h = self.layer_norm(attn(x), residual=x, name=pre("norm1"))
-        return self.layer_norm(ffn(h), residual=h, name=pre("norm2"))
+            h = self.add(x, attn(norm(x, "norm1")))
+            return self.add(h, ffw(norm(h, "norm2")))
+        h = norm(attn(x), "norm1", x)
+        return norm(ffw(h), "norm2", h)
 
     def _share(self, op, shared_op):
         """``shared_op`` (``src/runtime/model.cc:157-171``): the new op uses the weights of

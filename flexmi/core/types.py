@@ -132,6 +132,7 @@ class OperatorType(IntEnum):
     OP_ATTENTION = 105
     OP_LAYERNORM = 106
     OP_LINEAR_MX = 107
+    OP_GATED_LINEAR = 108
 
 
 class OpType(IntEnum):

@@ -10,5 +10,6 @@ from .cross import CrossCombine  # noqa
 from .attention import Attention  # noqa
 from .norm import LayerNorm  # noqa
 from .linear_mx import LinearMX  # noqa
+from .gated import GatedLinear  # noqa
 from .conv import Conv2D, Pool2D, BatchNorm  # noqa
 from .rnn import LSTM  # noqa

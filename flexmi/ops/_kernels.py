@@ -454,6 +454,30 @@ def mx_gemm(a, sa, fmt_a, b, sb, fmt_b, out, M, N, K, bias=None, act=10, beta=Fa
     C().mx_gemm(a, sa, int(fmt_a), b, sb, int(fmt_b), out, bias, int(act), bool(beta), int(M), int(N), int(K))
 
 
+# ------------------------------------------------------------------ gated feed-forward (csrc/kernels/glu.hip)
+def glu_gemm_eligible(x, w, gu, h):
+    """The fused forward takes these operands: bf16, ``F % 4 == 0``, ``H % 8 == 0``, row strides of ``x`` / ``h``
+    multiples of 8 / 4 elements, 16-byte aligned bases, contiguous ``w [2F, H]`` and ``gu [M, 2F]``."""
+    return bool(C().glu_gemm_eligible(x, w, gu, h))
+
+
+def glu_gemm_fwd(x, w, gu, h, act):
+    """``gu = x w^T`` rounded and stored, ``h = act(gu[:, :F]) * gu[:, F:]`` from the rounded values, in ONE MFMA
+    kernel; ``act`` 0 = SiLU, 1 = exact GELU.  ``x [M, H]`` and ``h [M, F]`` may be column slices of wider
+    buffers.  Raises on operands :func:`glu_gemm_eligible` refuses."""
+    C().glu_gemm_fwd(x, w, gu, h, int(act))
+
+
+def glu_act_fwd(gu, h, act):
+    """``h [M, F] = act(gu[:, :F]) * gu[:, F:]`` (bf16 or fp32, fp32 arithmetic, one rounding)."""
+    C().glu_act_fwd(gu, h, int(act))
+
+
+def glu_act_bwd(dh, gu, dgu, act):
+    """``dgu[:, :F] = dh * u * act'(g)`` and ``dgu[:, F:] = dh * act(g)`` with ``g, u`` the halves of ``gu``."""
+    C().glu_act_bwd(dh, gu, dgu, int(act))
+
+
 # ------------------------------------------------------------------ optimizers / loss
 def sgd_update(master, grad, v, compute, lr_tensor, wd, momentum, nesterov, zero_grad=False):
     """zero_grad: the kernel writes the consumed gradient back as zeros (no separate memset)."""

@@ -26,6 +26,8 @@ def _make_clone(op, m, in_shapes, out_shapes):
         m.dense(ins[0], out_shapes[0][-1], op.activation, op.use_bias)
     elif t == OperatorType.OP_LINEAR_MX:
         m.dense(ins[0], out_shapes[0][-1], op.activation, op.use_bias, fp8=True)
+    elif t == OperatorType.OP_GATED_LINEAR:
+        m.gated_dense(ins[0], out_shapes[0][-1], op.activation)
     elif t == OperatorType.OP_EMBEDDING:
         m.embedding(ins[0], op.num_entries, out_shapes[0][-1], op.aggr)
     elif t == OperatorType.OP_DOT_INTERACTION:
