@@ -1069,6 +1069,71 @@ void glu_act_bwd(torch::Tensor dh, torch::Tensor gu, torch::Tensor dgu, int64_t 
               "glu_act_bwd: refused (activation 0 / 1, row strides of at least the width)");
 }
 
+// ---- dense layer with GELU / tanh-GELU / SiLU (act_gemm.hip); code = the unary code 5 / 6 / 7 ------------
+// an optional contiguous fp32 [F] device vector (bias, its gradient)
+void act_vector(const char* fn, const c10::optional<torch::Tensor>& t, int64_t F, const char* what) {
+  if (!given(t)) return;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 && t->is_contiguous() && t->numel() == F, fn, " ", what,
+              ": contiguous fp32 [", F, "] device tensor expected");
+}
+
+// the fused forward would take these operands (shape, strides, alignment)
+bool act_gemm_eligible(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor pre, torch::Tensor y) {
+  if (!(x.is_cuda() && x.dim() == 2 && w.dim() == 2 && y.dim() == 2 && pre.dim() == 2 && x.stride(1) == 1 && y.stride(1) == 1 &&
+        is_bf16(x) && is_bf16(w) && is_bf16(pre) && is_bf16(y) && w.is_contiguous() && pre.is_contiguous()))
+    return false;
+  const int64_t M = x.size(0), H = x.size(1), F = y.size(1);
+  if (w.size(0) != F || w.size(1) != H || pre.size(0) != M || pre.size(1) != F || y.size(0) != M || F > INT32_MAX / 2 ||
+      H > INT32_MAX)
+    return false;
+  if (given(bias) && !(bias->is_cuda() && bias->scalar_type() == torch::kFloat32 && bias->is_contiguous() && bias->numel() == F))
+    return false;
+  return fm_act_gemm_eligible(x.data_ptr(), M > 1 ? x.stride(0) : H, w.data_ptr(), fptr(bias), pre.data_ptr(), y.data_ptr(),
+                              M > 1 ? y.stride(0) : F, M, (int)F, (int)H) != 0;
+}
+
+// pre = x w^T + bias (rounded, stored) and y = act(pre) in one kernel; bf16 only.  tile: 0 (default), 64 or 128
+void act_gemm_fwd(torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias, torch::Tensor pre, torch::Tensor y,
+                  int64_t code, int64_t tile) {
+  const int64_t F = y.dim() == 2 ? y.size(1) : 0;
+  glu_first("act_gemm_fwd", x, F);
+  TORCH_CHECK(is_bf16(x), "act_gemm_fwd: bf16 operands expected (fp32 takes the composed form)");
+  const int64_t M = x.size(0), H = x.size(1);
+  TORCH_CHECK(H >= 1 && H <= INT32_MAX, "act_gemm_fwd: bad H");
+  const int64_t ldx = glu_operand("act_gemm_fwd", x, M, H, torch::kBFloat16, "x");
+  const int64_t ldy = glu_operand("act_gemm_fwd", y, M, F, torch::kBFloat16, "y");
+  TORCH_CHECK(glu_operand("act_gemm_fwd", w, F, H, torch::kBFloat16, "w") == H && w.is_contiguous(),
+              "act_gemm_fwd w: contiguous [F, H] expected");
+  TORCH_CHECK(glu_operand("act_gemm_fwd", pre, M, F, torch::kBFloat16, "pre") == F && pre.is_contiguous(),
+              "act_gemm_fwd pre: contiguous [M, F] expected");
+  act_vector("act_gemm_fwd", bias, F, "bias");
+  TORCH_CHECK(fm_act_gemm_fwd(x.data_ptr(), ldx, w.data_ptr(), fptr(bias), pre.data_ptr(), y.data_ptr(), ldy, M, (int)F, (int)H,
+                              (int)code, (int)tile, cur()) == 0,
+              "act_gemm_fwd: operands outside the fused kernel's contract (F % 4, H % 8, row strides % 8 (x) / % 4 (y), "
+              "16-B aligned bases, activation code 5 / 6 / 7, tile 0 / 64 / 128)");
+}
+
+int64_t act_bwd_rows() { return fm_act_bwd_rows(); }
+
+// dpre = dy * act'(pre); db += its column sums in a fixed order (through the fp32 workspace ws)
+void act_bwd(torch::Tensor dy, torch::Tensor pre, torch::Tensor dpre, c10::optional<torch::Tensor> db,
+             c10::optional<torch::Tensor> ws, int64_t code) {
+  const int64_t F = dy.dim() == 2 ? dy.size(1) : 0;
+  glu_first("act_bwd", dy, F);
+  const int64_t M = dy.size(0);
+  const int64_t lddy = glu_operand("act_bwd", dy, M, F, dy.scalar_type(), "dy");
+  const int64_t ldp = glu_operand("act_bwd", pre, M, F, dy.scalar_type(), "pre");
+  const int64_t lddp = glu_operand("act_bwd", dpre, M, F, dy.scalar_type(), "dpre");
+  act_vector("act_bwd", db, F, "db");
+  if (given(db))
+    TORCH_CHECK(given(ws) && ws->is_cuda() && ws->scalar_type() == torch::kFloat32 && ws->is_contiguous(),
+                "act_bwd ws: contiguous fp32 device workspace expected with db");
+  const int st = fm_act_bwd(dy.data_ptr(), lddy, pre.data_ptr(), ldp, dpre.data_ptr(), lddp, fptr(db), fptr(ws),
+                            given(ws) ? ws->numel() * 4 : 0, M, (int)F, (int)code, is_bf16(dy), cur());
+  TORCH_CHECK(st == 0, "act_bwd: ", st == 2 ? "workspace smaller than ceil(M / act_bwd_rows()) * F floats"
+                                            : "refused (activation code 5 / 6 / 7, row strides of at least the width)");
+}
+
 void sgd(torch::Tensor W, torch::Tensor G, c10::optional<torch::Tensor> V, c10::optional<torch::Tensor> Wc, torch::Tensor lr,
          double wd, double mom, bool nesterov, bool zero_grad) {
   check_update("sgd", W, G, {V}, Wc, lr);
@@ -1865,6 +1930,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("glu_gemm_fwd", &glu_gemm_fwd);
   m.def("glu_act_fwd", &glu_act_fwd);
   m.def("glu_act_bwd", &glu_act_bwd);
+  m.def("act_gemm_eligible", &act_gemm_eligible);
+  m.def("act_gemm_fwd", &act_gemm_fwd);
+  m.def("act_bwd_rows", &act_bwd_rows);
+  m.def("act_bwd", &act_bwd);
   m.def("mx_quant", &mx_quant);
   m.def("mx_quant_dact", &mx_quant_dact);
   m.def("mx_gemm", &mx_gemm);

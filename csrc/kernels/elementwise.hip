@@ -9,17 +9,19 @@
 //   softmax            (softmax.cu cuDNN softmax; wave per row)
 //   dropout            (dropout.cu cuDNN; counter-based mask regenerated in backward: no mask buffer)
 // Storage type T is bf16 (unsigned short) or fp32, selected at launch.
-#include "common.h"
+#include "act_math.h"
 
 namespace {
 
 // ---------------------------------------------------------------- unary
+// codes 5..7 (GELU, tanh-GELU, SiLU; act_math.h) take their derivative from x, the others from y
 FM_DEVICE float un_f(int code, float x) {
   switch (code) {
     case 0: return x > 0.f ? x : 0.f;
     case 1: return 1.f / (1.f + __expf(-x));
     case 2: return tanhf(x);
     case 3: return x > 0.f ? x : expm1f(x);   // exp(x) - 1 cancels near 0 (22 % off at x = -1.5e-7)
+    case ACTZ_GELU: case ACTZ_GELU_TANH: case ACTZ_SILU: return actz_fwd(code, x);
     default: return __expf(x);
   }
 }
@@ -29,6 +31,7 @@ FM_DEVICE float un_b(int code, float x, float y, float dy) {
     case 1: return dy * y * (1.f - y);
     case 2: return dy * fmaf(-y, y, 1.f);   // one rounding: 1 - y*y in two loses the result where |y| -> 1
     case 3: return x > 0.f ? dy : dy * (y + 1.f);
+    case ACTZ_GELU: case ACTZ_GELU_TANH: case ACTZ_SILU: return dy * actz_dfwd(code, x);
     default: return dy * y;
   }
 }

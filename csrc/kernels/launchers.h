@@ -65,6 +65,17 @@ int fm_glu_act_fwd(const void* gu, long ldgu, void* h, long ldh, long M, int F, 
 int fm_glu_act_bwd(const void* dh, long lddh, const void* gu, long ldgu, void* dgu, long lddgu, long M, int F, int act,
                    int bf16, hipStream_t stream);
 
+// act_gemm.hip: dense layer with GELU / tanh-GELU / SiLU (code 5 / 6 / 7, the unary codes).  w [F][H] and pre [M][F]
+// are contiguous, bias is fp32 [F] or null.  The launchers return 0, or 1 when they refuse the operands (nothing is
+// launched then); fm_act_bwd returns 2 when ws holds fewer than ceil(M / fm_act_bwd_rows()) * F floats.
+int fm_act_gemm_eligible(const void* x, long ldx, const void* w, const float* bias, const void* pre, const void* y, long ldy,
+                         long M, int F, int H);
+int fm_act_gemm_fwd(const void* x, long ldx, const void* w, const float* bias, void* pre, void* y, long ldy, long M, int F,
+                    int H, int code, int tile, hipStream_t stream);
+int fm_act_bwd_rows();
+int fm_act_bwd(const void* dy, long lddy, const void* pre, long ldp, void* dpre, long lddp, float* db, float* ws,
+               long ws_bytes, long M, int F, int code, int bf16, hipStream_t stream);
+
 // embedding.hip
 void fm_embedding_fwd_multi(int n, const float* const* W, const void* const* idx, const int* idx64, void* const* out,
                             const long* ldo, const long* lo, const int* rows, const int* D, const int* bag,

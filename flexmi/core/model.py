@@ -27,6 +27,7 @@ from flexmi.ops.conv import BatchNorm, Conv2D, Pool2D
 from flexmi.ops.cross import CrossCombine
 from flexmi.ops.elementwise import ElementBinary, ElementUnary
 from flexmi.ops.embedding import Embedding
+from flexmi.ops.act_linear import ACT_CODES, ActLinear
 from flexmi.ops.gated import GatedLinear
 from flexmi.ops.linear import Linear
 from flexmi.ops.linear_mx import LinearMX, mx_eligible
@@ -152,6 +153,19 @@ class FFModel:
             return DeferredOp(self, lambda t: self.elu(t, name), 1, desc="elu")
         return self._add(ElementUnary(self, OperatorType.OP_ELU, x, name)).outputs[0]
 
+    def gelu(self, x=None, approximate=False, name=None):
+        """GELU as an :class:`ElementUnary` op: the exact erf form, or with ``approximate=True`` the tanh form
+        (torch's ``approximate="tanh"``).  The gradient is taken from the op's input."""
+        if x is None:
+            return DeferredOp(self, lambda t: self.gelu(t, approximate, name), 1, desc="gelu")
+        t = OperatorType.OP_GELU_TANH if approximate else OperatorType.OP_GELU
+        return self._add(ElementUnary(self, t, x, name)).outputs[0]
+
+    def silu(self, x=None, name=None):
+        if x is None:
+            return DeferredOp(self, lambda t: self.silu(t, name), 1, desc="silu")
+        return self._add(ElementUnary(self, OperatorType.OP_SILU, x, name)).outputs[0]
+
     def add(self, x=None, y=None, name=None):
         if x is None:
             return DeferredOp(self, lambda a, b: self.add(a, b, name), 2, desc="add")
@@ -186,6 +200,8 @@ class FFModel:
             return DeferredOp(self, lambda t: self.conv2d(t, out_channels, kernel_h, kernel_w, stride_h, stride_w,
                                                           padding_h, padding_w, activation, use_bias, None, ki, bi,
                                                           name, groups), 1, chk, "conv2d")
+        if activation in ACT_CODES:
+            raise ValueError(f"conv2d: {ActiMode(activation).name} is an activation of dense() only")
         op = Conv2D(self, input, out_channels, kernel_h, kernel_w, stride_h, stride_w, padding_h, padding_w,
                     activation, use_bias, kernel_initializer, bias_initializer, name, groups)
         self._share(op, shared_op)
@@ -212,6 +228,8 @@ class FFModel:
             ac = pool_type if pool_type in (ActiMode.AC_MODE_NONE, ActiMode.AC_MODE_RELU,
                                             ActiMode.AC_MODE_SIGMOID, ActiMode.AC_MODE_TANH) else ActiMode.AC_MODE_NONE
             return DeferredOp(self, lambda t: self.pool2d(t, *args, pt, ac, name), 1, desc="pool2d")
+        if activation in ACT_CODES:
+            raise ValueError(f"pool2d: {ActiMode(activation).name} is an activation of dense() only")
         return self._add(Pool2D(self, input, kernel_h, kernel_w, stride_h, stride_w, padding_h, padding_w,
                                 pool_type, activation, name)).outputs[0]
 
@@ -225,7 +243,12 @@ class FFModel:
               kernel_initializer=None, bias_initializer=None, name=None, fp8=None):
         """``fp8=True`` builds the layer in MXFP8 (:class:`flexmi.ops.linear_mx.LinearMX`; both widths must be
         multiples of 32, else ValueError), ``False`` an ordinary :class:`Linear`; ``None`` follows
-        ``FFConfig.linear_fp8`` (``--linear-fp8``), under which a layer of other widths quietly stays Linear."""
+        ``FFConfig.linear_fp8`` (``--linear-fp8``), under which a layer of other widths quietly stays Linear.
+
+        ``activation`` ``AC_MODE_GELU`` (exact erf form), ``AC_MODE_GELU_TANH`` or ``AC_MODE_SILU`` builds a
+        :class:`flexmi.ops.act_linear.ActLinear`, which keeps the pre-activation for a true backward; its weights,
+        names and checkpoint keys are Linear's.  There is no MXFP8 form of it: with ``fp8=True`` it is a ValueError,
+        under ``FFConfig.linear_fp8`` with ``fp8=None`` the layer quietly stays ActLinear."""
         if not _is_tensor(input):
             # functional form dense(in_dim, out_dim, act, use_bias, kernel_init, bias_init)
             # (include/model.h:432-436: no shared_op slot -> the 5th/6th args are the initialisers)
@@ -236,9 +259,14 @@ class FFModel:
                 assert t.dims[-1] == in_dim, f"dense: input has {t.dims[-1]} features, op built for {in_dim}"
             return DeferredOp(self, lambda t: self.dense(t, out_dim, activation, use_bias, None, ki, bi, name, fp8), 1, chk,
                               "dense")
-        if fp8 is None:
-            fp8 = getattr(self.config, "linear_fp8", False) and mx_eligible(input.dims[-1], int(out_dim))
-        cls = LinearMX if fp8 else Linear
+        if ActiMode(activation) in ACT_CODES:
+            if fp8:
+                raise ValueError(f"dense(fp8=True): no MXFP8 form of a layer with {ActiMode(activation).name}")
+            cls = ActLinear
+        else:
+            if fp8 is None:
+                fp8 = getattr(self.config, "linear_fp8", False) and mx_eligible(input.dims[-1], int(out_dim))
+            cls = LinearMX if fp8 else Linear
         op = cls(self, input, out_dim, activation, use_bias, kernel_initializer, bias_initializer, name)
         self._share(op, shared_op)
         return self._add(op).outputs[0]
@@ -392,8 +420,15 @@ class FFModel:
 
         ``ffn="swiglu"`` / ``"geglu"`` builds ``<name>_ff1`` as :meth:`gated_dense` (``dim_feedforward`` wide, SiLU /
         GELU gate, no bias) instead of the ReLU :meth:`dense`; ``fp8`` then goes to ``<name>_ff2`` only.  Any other
-        string than these and ``"relu"`` is a ValueError.  ``rms_norm=True`` makes both norms RMSNorm;
-        ``ffn_bias=False`` builds the feed-forward :meth:`dense` ops without bias.
+        string than these, ``"relu"`` and the three below is a ValueError.  ``rms_norm=True`` makes both norms
+        RMSNorm; ``ffn_bias=False`` builds the feed-forward :meth:`dense` ops without bias.
+
+        ``ffn="gelu"`` / ``"gelu_tanh"`` / ``"silu"`` builds ``<name>_ff1`` as a :meth:`dense` with ``AC_MODE_GELU`` /
+        ``AC_MODE_GELU_TANH`` / ``AC_MODE_SILU`` (an ``ActLinear``; ``fp8`` then goes to ``<name>_ff2`` only).  With
+        ``ffn="gelu"`` the weights map to ``torch.nn.TransformerEncoderLayer(E, num_heads, dim_feedforward, dropout=0,
+        activation="gelu", batch_first=True, norm_first=norm_first)`` exactly as above: ``<name>_ff1.weight / .bias`` =
+        ``linear1.weight / .bias``, ``<name>_ff2`` = ``linear2``.  ``"gelu_tanh"`` is GPT-2's ``gelu_new`` MLP
+        (``c_fc.weight`` transposed to [out, in]).
 
         A Hugging Face Llama decoder layer is ``norm_first=True, rms_norm=True, ffn="swiglu", ffn_bias=False,
         attention_bias=False, causal=True, rope_base=..., num_kv_heads=...``: ``<name>_norm1.scale`` =
@@ -402,16 +437,20 @@ class FFModel:
         ``<name>_ff1.kernel`` = ``mlp.gate_proj.weight`` and rows ``[F, 2F)`` = ``mlp.up_proj.weight`` (``F =
         dim_feedforward``), ``<name>_ff2.weight`` = ``mlp.down_proj.weight``.  The norms use
         ``eps = 1e-5``; a model with another ``rms_norm_eps`` is built from the layer's parts."""
-        if ffn not in ("relu", "swiglu", "geglu"):
-            raise ValueError(f"transformer_encoder_layer: ffn {ffn!r}; 'relu', 'swiglu' or 'geglu' expected")
+        acts = {"relu": ActiMode.AC_MODE_RELU, "gelu": ActiMode.AC_MODE_GELU, "gelu_tanh": ActiMode.AC_MODE_GELU_TANH,
+                "silu": ActiMode.AC_MODE_SILU}
+        if ffn not in acts and ffn not in ("swiglu", "geglu"):
+            raise ValueError(f"transformer_encoder_layer: ffn {ffn!r}; 'relu', 'gelu', 'gelu_tanh', 'silu', 'swiglu' or "
+                             f"'geglu' expected")
         E = x.dims[-1]
         pre = (lambda s: None) if name is None else (lambda s: f"{name}_{s}")
         attn = lambda t: self.multihead_attention(t, t, t, E, num_heads, bias=attention_bias, causal=causal,  # noqa: E731
                                                   name=pre("attn"), fp8=fp8, num_kv_heads=num_kv_heads,
                                                   key_lengths=key_lengths, rope_base=rope_base,
                                                   rope_interleaved=rope_interleaved)
-        if ffn == "relu":
-            ff1 = lambda t: self.dense(t, dim_feedforward, ActiMode.AC_MODE_RELU, ffn_bias, name=pre("ff1"), fp8=fp8)  # noqa: E731
+        if ffn in acts:
+            ff1 = lambda t: self.dense(t, dim_feedforward, acts[ffn], ffn_bias, name=pre("ff1"),  # noqa: E731
+                                       fp8=fp8 if ffn == "relu" else None)
         else:
             ff1 = lambda t: self.gated_dense(t, dim_feedforward, "silu" if ffn == "swiglu" else "gelu", name=pre("ff1"))  # noqa: E731
         ffw = lambda t: self.dense(ff1(t), E, use_bias=ffn_bias, name=pre("ff2"), fp8=fp8)  # noqa: E731

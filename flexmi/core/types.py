@@ -15,6 +15,10 @@ class ActiMode(IntEnum):
     AC_MODE_RELU = 11
     AC_MODE_SIGMOID = 12
     AC_MODE_TANH = 13
+    # flexmi extensions (the reference stops at 13): dense() builds them as flexmi.ops.act_linear.ActLinear
+    AC_MODE_GELU = 14          # exact erf form, torch's default
+    AC_MODE_GELU_TANH = 15     # approximate="tanh", GPT-2's
+    AC_MODE_SILU = 16
 
 
 class AggrMode(IntEnum):
@@ -133,6 +137,10 @@ class OperatorType(IntEnum):
     OP_LAYERNORM = 106
     OP_LINEAR_MX = 107
     OP_GATED_LINEAR = 108
+    OP_LINEAR_ACT = 109
+    OP_GELU = 110
+    OP_GELU_TANH = 111
+    OP_SILU = 112
 
 
 class OpType(IntEnum):

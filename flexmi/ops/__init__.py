@@ -11,5 +11,6 @@ from .attention import Attention  # noqa
 from .norm import LayerNorm  # noqa
 from .linear_mx import LinearMX  # noqa
 from .gated import GatedLinear  # noqa
+from .act_linear import ActLinear  # noqa
 from .conv import Conv2D, Pool2D, BatchNorm  # noqa
 from .rnn import LSTM  # noqa

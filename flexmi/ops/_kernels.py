@@ -478,6 +478,37 @@ def glu_act_bwd(dh, gu, dgu, act):
     C().glu_act_bwd(dh, gu, dgu, int(act))
 
 
+# ------------------------------------------------------------------ dense + GELU / SiLU (csrc/kernels/act_gemm.hip)
+def act_gemm_eligible(x, w, bias, pre, y):
+    """The fused forward takes these operands: bf16, ``F % 4 == 0``, ``H % 8 == 0``, row strides of ``x`` / ``y``
+    multiples of 8 / 4 elements, 16-byte aligned bases, contiguous ``w [F, H]`` and ``pre [M, F]``, ``bias`` fp32
+    ``[F]`` or None."""
+    return bool(C().act_gemm_eligible(x, w, bias, pre, y))
+
+
+def act_gemm_fwd(x, w, bias, pre, y, code, tile=0):
+    """``pre = x w^T + bias`` rounded and stored, ``y = act(pre)`` from the rounded values, in ONE MFMA kernel;
+    ``code`` is the unary code 5 = exact GELU, 6 = tanh GELU, 7 = SiLU.  ``x [M, H]`` and ``y [M, F]`` may be column
+    slices of wider buffers.  ``tile`` 64 / 128 forces the block tile's columns (0: the default).  Raises on operands
+    :func:`act_gemm_eligible` refuses."""
+    C().act_gemm_fwd(x, w, bias, pre, y, int(code), int(tile))
+
+
+def act_bwd_rows():
+    """Rows of ``dpre`` one block of :func:`act_bwd` sums into one partial row of the bias gradient."""
+    return int(C().act_bwd_rows())
+
+
+def act_bwd(dy, pre, dpre, db, code):
+    """``dpre = dy * act'(pre)`` (bf16 or fp32, fp32 arithmetic, one rounding); ``db +=`` the column sums of the fp32
+    products (fp32 ``[F]``; None: not formed) in a fixed order, through the per-device workspace."""
+    ws = None
+    if db is not None:
+        need = (dy.shape[0] + act_bwd_rows() - 1) // act_bwd_rows() * dy.shape[1] * 4
+        ws = workspace(dy.device, max(GEMM_WS_BYTES, need))
+    C().act_bwd(dy, pre, dpre, db, ws, int(code))
+
+
 # ------------------------------------------------------------------ optimizers / loss
 def sgd_update(master, grad, v, compute, lr_tensor, wd, momentum, nesterov, zero_grad=False):
     """zero_grad: the kernel writes the consumed gradient back as zeros (no separate memset)."""

@@ -4,8 +4,12 @@ Reference: ``src/ops/element_unary.cu`` (cuDNN activations + custom ``exp`` kern
 ``:384-404``) and ``src/ops/element_binary.cu`` (cuDNN OpTensor ADD/MUL, SUB via α=-1, DIV
 asserts -- caveat C9).  MI355X: vectorised HIP kernels ``csrc/kernels/elementwise.hip`` for all
 of relu/sigmoid/tanh/elu/exp and add/sub/mul/div (DIV works).  Any dim may be split.
+GELU (exact and tanh form) and SiLU are flexmi extensions (``OP_GELU`` / ``OP_GELU_TANH`` / ``OP_SILU``, unary
+codes 5-7; ``csrc/kernels/act_math.h``): their gradient is taken from the op's input.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -13,16 +17,29 @@ from flexmi.core.types import OperatorType
 from flexmi.parallel.layout import Layout
 
 from .base import Op, OpCtx, store
+from .gated import glu_act_torch
 from . import _kernels as K
 
 UNARY_CODES = {OperatorType.OP_RELU: 0, OperatorType.OP_SIGMOID: 1, OperatorType.OP_TANH: 2,
-               OperatorType.OP_ELU: 3, OperatorType.OP_EXP: 4}
+               OperatorType.OP_ELU: 3, OperatorType.OP_EXP: 4,
+               OperatorType.OP_GELU: 5, OperatorType.OP_GELU_TANH: 6, OperatorType.OP_SILU: 7}
 BINARY_CODES = {OperatorType.OP_EW_ADD: 0, OperatorType.OP_EW_SUB: 1, OperatorType.OP_EW_MUL: 2,
                 OperatorType.OP_EW_DIV: 3}
 _UNARY_NAMES = {OperatorType.OP_RELU: "Relu", OperatorType.OP_SIGMOID: "Sigmoid",
-                OperatorType.OP_TANH: "Tanh", OperatorType.OP_ELU: "Elu", OperatorType.OP_EXP: "Exp"}
+                OperatorType.OP_TANH: "Tanh", OperatorType.OP_ELU: "Elu", OperatorType.OP_EXP: "Exp",
+                OperatorType.OP_GELU: "Gelu", OperatorType.OP_GELU_TANH: "GeluTanh", OperatorType.OP_SILU: "Silu"}
 _BINARY_NAMES = {OperatorType.OP_EW_ADD: "Add", OperatorType.OP_EW_SUB: "Sub",
                  OperatorType.OP_EW_MUL: "Mul", OperatorType.OP_EW_DIV: "Div"}
+
+
+def actz_torch(code, z):
+    """fp32 ``act(z)`` and ``act'(z)`` of the codes 5 (exact GELU), 6 (tanh GELU) and 7 (SiLU), written out (no
+    autograd): none of them is monotonic, so the derivative is a function of the input, not of the output"""
+    if code == 6:
+        k = math.sqrt(2 / math.pi)
+        t = torch.tanh(k * (z + 0.044715 * z ** 3))
+        return 0.5 * z * (1 + t), 0.5 * (1 + t) + 0.5 * z * (1 - t * t) * k * (1 + 3 * 0.044715 * z * z)
+    return glu_act_torch(z, "silu" if code == 7 else "gelu")
 
 
 def unary_fwd_torch(code, x):
@@ -34,6 +51,8 @@ def unary_fwd_torch(code, x):
         return torch.tanh(x)
     if code == 3:
         return torch.nn.functional.elu(x)
+    if code >= 5:
+        return actz_torch(code, x)[0]
     return torch.exp(x)
 
 
@@ -46,6 +65,8 @@ def unary_bwd_torch(code, x, y, dy):
         return dy * (1 - y * y)
     if code == 3:
         return dy * torch.where(x > 0, torch.ones_like(x), y + 1)
+    if code >= 5:
+        return dy * actz_torch(code, x)[1]
     return dy * y
 
 

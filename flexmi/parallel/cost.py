@@ -115,6 +115,13 @@ class CostModel:
             ew = self._bytes_us(3 * M * F * eb)
             return (L + self._gemm_us(M, 2 * F, K) + ew,
                     3 * L + self._gemm_us(2 * F, K, M) + self._gemm_us(M, K, 2 * F) + ew)
+        if t == OperatorType.OP_LINEAR_ACT:
+            # a Linear plus one pass over pre [M, F] and y [M, F] each way (not a measured entry)
+            K = in_shapes[0][-1]
+            F = out_shapes[0][-1]
+            M = _prod(out_shapes[0][:-1])
+            ew = self._bytes_us(2 * M * F * eb)
+            return (L + self._gemm_us(M, F, K) + ew, 3 * L + self._gemm_us(F, K, M) + self._gemm_us(M, K, F) + ew)
         if t == OperatorType.OP_EMBEDDING:
             B = in_shapes[0][0]
             bag = in_shapes[0][1] if len(in_shapes[0]) > 1 else 1
@@ -168,6 +175,8 @@ class CostModel:
             return 3.0, 3.0 if op.inputs[0].owner_op is None else 4.0
         if t == OperatorType.OP_GATED_LINEAR:   # fused forward (composed: two); act-bwd and two GEMMs
             return 1.0, 2.0 if op.inputs[0].owner_op is None else 3.0
+        if t == OperatorType.OP_LINEAR_ACT:   # GEMM + unary (fused: one); act-bwd, fold and two GEMMs
+            return 2.0, 3.0 if op.inputs[0].owner_op is None else 4.0
         if t == OperatorType.OP_EMBEDDING:
             return 0.25, 0.25
         if t in (OperatorType.OP_CONV2D,):

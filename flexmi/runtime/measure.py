@@ -22,7 +22,7 @@ def _make_clone(op, m, in_shapes, out_shapes):
     from flexmi.ops.elementwise import ElementBinary, ElementUnary
     t = op.op_type
     ins = [m.create_tensor(list(s), op.inputs[i].data_type) for i, s in enumerate(in_shapes)]
-    if t == OperatorType.OP_LINEAR:
+    if t in (OperatorType.OP_LINEAR, OperatorType.OP_LINEAR_ACT):   # the activation picks the class
         m.dense(ins[0], out_shapes[0][-1], op.activation, op.use_bias)
     elif t == OperatorType.OP_LINEAR_MX:
         m.dense(ins[0], out_shapes[0][-1], op.activation, op.use_bias, fp8=True)
